@@ -9,16 +9,24 @@ and the Riccati form with its factorization on MFMA above; extraction), and for 
 all-gather of the solved forces over xGMI (north_star, config C3).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--horizon 10]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the seeded batch, warms up,
+times the K steps and prints ONE JSON line (value, ms_per_step, the roofline of the timed kernels
+from their HIP-event span, iteration statistics).  --dump-outputs DIR then also writes the results of
+the last timed step, one DIR/<field>.npy per mpcqp_result field in float64 (see dump_outputs).
+Everything else -- the CPU oracle legs (parity sample, cpu_baseline) and, at N = 1, the extra keys
+below, each a measurement of its own -- runs only with --full.
 
 --gpus N > 1 without a torch.distributed environment: this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child (it never touches the
 GPU itself) and exits with the child's code.  Every rank takes the contiguous shard
 shard_range(N*B, N, rank) of ONE seeded global batch of N*B robots (weak scaling: B robots per GPU,
 8192 by default when N > 1, so --gpus 8 is C3's 65536 robots), solves it and all-gathers u0 with mpcqp.distributed.allgather_forces.
-Rank 0 checks the world size, checks the gathered forces against the CPU oracle on a 4096-robot
-sample spread over every shard, and prints ONE JSON line.
+Rank 0 checks the world size, with --full checks the gathered forces against the CPU oracle on a
+4096-robot sample spread over every shard, and prints ONE JSON line.
 
-At N = 1 the line also carries the CPU baseline (the oracle on the host cores) and extra keys,
+With --full at N = 1 the line also carries the CPU baseline (the oracle on the host cores) and extra keys,
 each with its own parity sample: e2e (host buffers in and out through mpcqp_solve_batch_host),
 assemble_e2e (raw robot-state rows -> on-device assembly -> solve), c4 (horizon 20), c5 (mixed
 gait, random mu, 8192 robots), c3_shard (one GPU's 8192-robot share of C3), batch_scaling (4096 to
@@ -43,6 +51,7 @@ PARITY_SAMPLE = 4096
 C2_BATCH = 4096           # BASELINE configs[1]: 4096 robots on one MI355X
 C3_BATCH_PER_GPU = 8192   # BASELINE configs[2]: 65536 robots sharded over 8 MI355X
 C3_GPUS = 8
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def algorithmic_flops(N, iters, rho_updates):
@@ -121,8 +130,15 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-sample", type=int, default=4096,
                     help="instances timed on the CPU oracle (4096 x ~2.3 ms = ~10 s of CPU work)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: min(16, usable cpus)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the e2e / c4 / c5 / warm_tick keys")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU oracle legs (parity "
+                         "sample, cpu_baseline) and the extra keys (e2e, assemble_e2e, two_streams, c5, "
+                         "c3_shard, batch_scaling, c4, warm_tick)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step as DIR/<field>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU oracle legs")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the e2e / c4 / c5 / warm_tick keys")
     ap.add_argument("--dist", action="store_true",
                     help="take the distributed branch (process group, per-step all-gather, allgather_ms, "
                          "gathered parity) at any world size, --gpus 1 included: a world-1 RCCL run on one "
@@ -187,6 +203,22 @@ def stub_results(recs):
 def as_rows(res):
     """mpcqp_result structured array -> [B, 30] float64 rows (bit copy) and back."""
     return np.frombuffer(res.tobytes(), dtype=np.float64).reshape(len(res), -1)
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what a caller of the timed path holds after its last step, one file per field
+    of the mpcqp_result rows (u0, f_body: [B, 12]; obj_val, pri_res, dua_res, rho, status, iters,
+    rho_updates, nan_legs: [B]), all float64 (the int32 fields convert exactly).  Above
+    DUMP_MAX_BYTES in all, a fixed seeded sample of the robots is written, their indices in rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    per_robot = 8 * (1 + sum(int(np.prod(res.dtype[n].shape, dtype=np.int64)) for n in res.dtype.names))
+    cap = DUMP_MAX_BYTES // per_robot
+    if len(res) > cap:
+        rows = np.sort(np.random.default_rng(0).choice(len(res), size=cap, replace=False))
+        res = res[rows]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    for name in res.dtype.names:
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(res[name], dtype=np.float64))
 
 
 def run_rank(args):
@@ -293,6 +325,13 @@ def run_rank(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        # the last timed step's result rows (the all-gather measurement below solves again)
+        d_last = d_res.clone()
+        last_rows = (allgather_forces(d_last, total) if dist_on else d_last).cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, np.frombuffer(np.ascontiguousarray(last_rows).tobytes(),
+                                                          dtype=mpcqp.RESULT_DTYPE))
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in events])) if events else None
     gather_ms = None
     if dist_on:
@@ -389,7 +428,7 @@ def run_rank(args):
                          + "; FLOPs = SURVEY §8(d)'s structure-exploiting count per robot with its actual "
                            "iterations and rho updates; peak = FP64 vector spec (= FP64 MFMA peak on gfx950)")}
             pyoracle = None
-            if not args.no_cpu:
+            if args.full and not args.no_cpu:
                 pyoracle = oracle_module()
                 op = pyoracle.default_params(N, q=list(params.q_weights), r=list(params.r_weights))
                 S = min(PARITY_SAMPLE, total)
@@ -407,7 +446,7 @@ def run_rank(args):
                             "mean_rho_updates": float(res_all["rho_updates"].mean()),
                             "solved_frac": float(np.mean(res_all["status"] == 1)),
                             "handoff_count": list(solver.handoff_counts()) if N <= 10 else None}
-            if not dist_on and not args.no_extras:
+            if args.full and not dist_on and not args.no_extras:
                 out["extras"] = extras(args, solver, params, recs_np, states, local_res, pyoracle, dev)
     if solver is not None:
         solver.close()

@@ -63,7 +63,7 @@ def test_shard_range_partitions():
 
 
 @pytest.mark.parametrize("world,batch", [(1, 32), (2, 48), (3, 16), (8, None)])
-def test_bench_launcher_shards_and_gathers(world, batch):
+def test_bench_launcher_shards_and_gathers(world, batch, tmp_path):
     """bench.py --gpus N as the driver runs it: the parent starts torch.distributed.run as a child
     (no GPU touched), N ranks take contiguous shards of ONE seeded global batch, run the production
     per-step call path (solve -> mpcqp.distributed.allgather_forces, here over gloo with a CPU stub
@@ -73,7 +73,7 @@ def test_bench_launcher_shards_and_gathers(world, batch):
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     argv = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(world), "--cpu-stub",
-            "--steps", "2", "--warmup", "1"]
+            "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")]
     if world == 1:  # the distributed branch at world 1 (what tests/test_gpu_rccl.py runs over RCCL)
         argv.append("--dist")
     if batch is not None:
@@ -90,6 +90,12 @@ def test_bench_launcher_shards_and_gathers(world, batch):
     assert rec["parity"]["gather_exact"] and rec["parity"]["instances"] == world * batch
     assert rec["value"] > 0 and rec["scaling"] == "weak"
     assert rec["extras"]["allgather_ms"] >= 0.0
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    u0 = np.load(tmp_path / "dump" / "u0.npy")  # rank 0 writes the whole batch's last-step results
+    import bench
+    assert u0.dtype == np.float64 and u0.shape == (world * batch, 12)
+    assert np.array_equal(u0, bench.stub_results(bench.workload(10, world * batch, "trot", False)[1])["u0"])
+    assert np.array_equal(np.load(tmp_path / "dump" / "iters.npy"), np.full(world * batch, 25.0))
     if world == 8:
         assert rec["config"]["global_batch"] == 65536 and rec["config"]["workload"].startswith("C3:")
 
@@ -102,6 +108,39 @@ def test_bench_default_batch_is_c2_at_one_gpu_and_c3_shard_above():
     assert bench.config_name(10, 4096, 1, "trot", False) == "C2"
     assert bench.config_name(10, 8192, 8, "trot", False) == "C3"
     assert bench.config_name(20, 4096, 1, "trot", False) == "C4"
+
+
+def test_bench_full_and_dump_options_parse():
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_fields_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per mpcqp_result field with the values of the rows; above the
+    size cap the same seeded sample of robots every time, their indices in rows.npy."""
+    import bench
+    import mpcqp
+    res = bench.stub_results(np.arange(50 * 60, dtype=np.float64).reshape(50, 60))
+    res["iters"] = np.arange(50)
+    bench.dump_outputs(str(tmp_path / "all"), res)
+    names = sorted(p.name[:-4] for p in (tmp_path / "all").iterdir())
+    assert names == sorted(mpcqp.RESULT_DTYPE.names)
+    for n in names:
+        a = np.load(tmp_path / "all" / (n + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, res[n])
+    per_robot = 8 * (1 + 12 + 12 + 8)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * per_robot)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), res)
+    rows = np.load(tmp_path / "s1" / "rows.npy").astype(np.int64)
+    assert len(rows) == 10 and len(set(rows)) == 10 and np.array_equal(rows, np.sort(rows))
+    assert sum(p.stat().st_size - 128 for p in (tmp_path / "s1").iterdir()) <= 10 * per_robot
+    for n in names:
+        a = np.load(tmp_path / "s1" / (n + ".npy"))
+        assert np.array_equal(a, res[n][rows]) and np.array_equal(a, np.load(tmp_path / "s2" / (n + ".npy")))
 
 
 def _fg_worker(rank, world, port, total, steps, out_dir):

@@ -36,7 +36,7 @@ def _bench(*args, timeout=300):
 
 
 def test_bench_rccl_world1_gathers_and_matches_oracle():
-    rec = _bench("--gpus", "1", "--dist", "--steps", "4", "--warmup", "1", "--batch", "2048")
+    rec = _bench("--gpus", "1", "--dist", "--full", "--steps", "4", "--warmup", "1", "--batch", "2048")
     print(json.dumps({k: rec[k] for k in ("value", "ms_per_step", "extras", "parity")}))
     assert rec["n_gpus"] == 1 and rec["config"]["ranks_seen"] == 1
     assert rec["config"]["collective"].startswith("RCCL")

@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -q --maxfail=20 --timeout 120
 rc=$?
 tail -25 "$OUT/gpu_tests.txt"
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 200 python bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+timeout -k 10 200 python bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run \
   -- python3 bench.py --steps 10 --warmup 2 --no-cpu --no-extras "$@" > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err" || exit $?
 python3 - "$OUT" << 'PY'
