@@ -519,6 +519,48 @@ int32_t mpcqp_copy_warm_slots_device(int32_t horizon, const double* d_src, const
              : MPCQP_ERR_HIP;
 }
 
+void mpcqp_plan_default_params(mpcqp_plan_params* p) {
+  if (!p) return;
+  const double sx[4] = {0.17, 0.17, -0.17, -0.17}, sy[4] = {0.15, -0.15, 0.15, -0.15};  // A1CtrlStates.h:45-47
+  const double kp[3] = {300.0, 400.0, 400.0}, kd[3] = {8.0, 8.0, 8.0};                  // :105-111
+  const double gc0[4] = {0.0, 120.0, 120.0, 0.0};                                       // :325
+  for (int i = 0; i < 4; ++i) {
+    p->default_foot_pos[3 * i] = sx[i];
+    p->default_foot_pos[3 * i + 1] = sy[i];
+    p->default_foot_pos[3 * i + 2] = -0.35;
+    for (int k = 0; k < 3; ++k) {
+      p->kp_foot[3 * i + k] = kp[k];
+      p->kd_foot[3 * i + k] = kd[k];
+    }
+    p->gait_counter_speed[i] = 2.0;  // :103
+    p->gait_counter_init[i] = gc0[i];
+  }
+  p->counter_per_gait = 120 * 2;     // :24
+  p->counter_per_swing = 120;        // :25
+  p->control_dt = 0.5 / 1000.0;      // :333, MAIN_UPDATE_FREQUENCY (A1Params.h:11)
+  p->foot_force_low = 30.0;          // A1Params.h:38
+  p->foot_delta_x_limit = 0.1;       // A1Params.h:44
+  p->foot_delta_y_limit = 0.1;       // A1Params.h:45
+  p->swing_clearance1 = (double)0.0f;  // A1Params.h:41
+  p->swing_clearance2 = (double)0.4f;  // A1Params.h:42
+  p->terrain = 1;                    // stance_leg_control_type, A1CtrlStates.h:21
+  p->use_terrain_adapt = 1;          // A1CtrlStates.h:22
+}
+
+int32_t mpcqp_plan_state_size(void) { return mpcqp::plan_state_doubles(); }
+
+int32_t mpcqp_leg_plan_device(const mpcqp_plan_params* pp, double dt, double* d_states, const double* d_plan_in,
+                              int32_t batch, double* d_plan_state, double* d_tq_records, double* d_plan_out,
+                              void* stream) {
+  if (!pp || batch < 0 || !(dt > 0.0) || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_states || !d_plan_in || !d_plan_state)) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_leg_plan(*pp, dt, d_states, d_plan_in, batch, d_plan_state, d_tq_records, d_plan_out, stream) ==
+                 hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
 void mpcqp_balance_default_params(mpcqp_balance_params* p) {
   if (!p) return;
   const double q[6] = {1.0, 1.0, 1.0, 400.0, 400.0, 100.0};  // A1RobotControl.cpp:11

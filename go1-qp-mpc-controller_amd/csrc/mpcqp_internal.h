@@ -66,6 +66,11 @@ hipError_t launch_assemble(int horizon, const double* states, int batch, double*
 hipError_t launch_copy_slots(const double* src, const int* sidx, double* dst, const int* didx, int count, int slot,
                              void* stream);
 
+// Upstream leg plan: gait, footholds, swing-leg PD force, contacts, terrain fit (mpcqp_legplan.hip)
+hipError_t launch_leg_plan(const mpcqp_plan_params& pp, double dt, double* states, const double* plan_in, int batch,
+                           double* slots, double* tq, double* out, void* stream);
+int plan_state_doubles();  // doubles per robot of the plan slot
+
 // Single-step QP balance controller (mpcqp_balance.hip)
 hipError_t launch_balance(const mpcqp_balance_params& bp, const mpcqp_params& p, const double* recs, int batch,
                           mpcqp_result* out, void* stream);

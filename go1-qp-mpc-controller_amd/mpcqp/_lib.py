@@ -32,6 +32,11 @@ ST_EULER_D, ST_POS_D, ST_ANG_VEL_D, ST_LIN_VEL_D, ST_FEET = 21, 24, 27, 30, 33
 ST_MASS, ST_INERTIA, ST_MU, ST_FZMIN, ST_FZMAX, ST_DT, ST_CONTACTS, ST_SIZE = 45, 46, 55, 56, 57, 58, 59, 64
 # torque-map record layout (include/mpcqp.h MPCQP_TQ_*)
 TQ_JFOOT, TQ_FKIN, TQ_KM, TQ_GRAV, TQ_CONTACTS, TQ_SIZE = 0, 36, 48, 51, 63, 68
+# leg-plan input row and window sizes (include/mpcqp.h MPCQP_PL_*, MPCQP_PLAN_*; the output row is
+# legplan.PLAN_OUT_DTYPE)
+PL_ROT_Z, PL_FOOT_FORCE, PL_MOVEMENT_MODE, PL_SIZE = 0, 9, 13, 16
+PO_SIZE = 108
+PLAN_CONTACT_WINDOW, PLAN_TERRAIN_WINDOW = 60, 100
 
 
 def rec_feet(N):
@@ -78,6 +83,19 @@ class BalanceParams(ctypes.Structure):
                 ("f_min", ctypes.c_double), ("f_max", ctypes.c_double)]
 
 
+class PlanParams(ctypes.Structure):
+    """mpcqp_plan_params."""
+    _fields_ = [
+        ("default_foot_pos", ctypes.c_double * 12), ("kp_foot", ctypes.c_double * 12),
+        ("kd_foot", ctypes.c_double * 12), ("gait_counter_speed", ctypes.c_double * 4),
+        ("gait_counter_init", ctypes.c_double * 4), ("counter_per_gait", ctypes.c_double),
+        ("counter_per_swing", ctypes.c_double), ("control_dt", ctypes.c_double),
+        ("foot_force_low", ctypes.c_double), ("foot_delta_x_limit", ctypes.c_double),
+        ("foot_delta_y_limit", ctypes.c_double), ("swing_clearance1", ctypes.c_double),
+        ("swing_clearance2", ctypes.c_double), ("terrain", ctypes.c_int32), ("use_terrain_adapt", ctypes.c_int32),
+    ]
+
+
 class Result(ctypes.Structure):
     """mpcqp_result."""
     _fields_ = [
@@ -108,6 +126,7 @@ EXPORTED = [
     "mpcqp_debug_scale_image_doubles", "mpcqp_debug_scale_image_device", "mpcqp_copy_warm_slots_device",
     "mpcqp_handoff_counts",
     "mpcqp_debug_set_split", "mpcqp_debug_split_parts",
+    "mpcqp_plan_default_params", "mpcqp_plan_state_size", "mpcqp_leg_plan_device",
 ]
 
 _libs = {}
@@ -189,6 +208,12 @@ def load(debug=False):
     L.mpcqp_debug_set_split.restype = i32
     L.mpcqp_debug_split_parts.argtypes = [vp, i32]
     L.mpcqp_debug_split_parts.restype = i32
+    L.mpcqp_plan_default_params.argtypes = [ctypes.POINTER(PlanParams)]
+    L.mpcqp_plan_default_params.restype = None
+    L.mpcqp_plan_state_size.argtypes = []
+    L.mpcqp_plan_state_size.restype = i32
+    L.mpcqp_leg_plan_device.argtypes = [ctypes.POINTER(PlanParams), ctypes.c_double, vp, vp, i32, vp, vp, vp, vp]
+    L.mpcqp_leg_plan_device.restype = i32
     ps, rs = i32(0), i32(0)
     L.mpcqp_abi_sizes(ctypes.byref(ps), ctypes.byref(rs))
     if ps.value != ctypes.sizeof(Params) or rs.value != ctypes.sizeof(Result):

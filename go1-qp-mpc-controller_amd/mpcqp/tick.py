@@ -7,14 +7,20 @@ persistent warm-started solver of A1RobotControl.h:67) followed by compute_joint
 (:289-319), three kernels on one stream with no host round trip.  ``capture()`` records the tick
 as a HIP graph (torch.cuda.CUDAGraph is hipGraph on ROCm), so a simulator steps with one replay.
 torch is used only to own device buffers and the capture stream.
+
+With ``plan`` (a PlanParams) the tick starts one stage earlier, with the leg plan (update_plan,
+generate_swing_legs_ctrl and the terrain adaptation of compute_grf, A1RobotControl.cpp:148-287,
+:335-376): it fills the contacts, the swing-leg force and root_euler_d[1] of ``states`` /
+``tq_records`` on the device from ``plan_in``, so the caller writes only sensor-level state.
 """
 from . import _lib
+from .legplan import leg_plan_device, plan_state_size
 from .solver import MpcQpSolver
 from .torques import joint_torques_device
 
 
 class ControlTick:
-    def __init__(self, batch, params=None, device=0):
+    def __init__(self, batch, params=None, device=0, plan=None, dt=None):
         import torch
         self.torch = torch
         self.B = int(batch)
@@ -30,11 +36,20 @@ class ControlTick:
         self.results = torch.zeros((self.B, _lib.RESULT_DOUBLES), **f64)
         self.counter = torch.zeros((self.B,), dtype=torch.int32, device=dev)
         self.torques = torch.zeros((self.B, 12), **f64)
+        self.plan = plan
+        if plan is not None:
+            self.dt = float(plan.control_dt if dt is None else dt)  # update_plan's dt argument
+            self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)   # caller writes rot_z / foot_force / mode
+            self.plan_state = torch.zeros((self.B, plan_state_size()), **f64)  # zero = reset() controller
+            self.plan_out = torch.zeros((self.B, _lib.PO_SIZE), **f64)
         self.graph = None
 
     def step(self, stream=None):
         """Enqueue one tick on `stream` (default: torch's current stream)."""
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        if self.plan is not None:
+            leg_plan_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
+                            self.plan_state.data_ptr(), self.tq_records.data_ptr(), self.plan_out.data_ptr(), s)
         _lib.assemble_records_device(self.solver.horizon, self.states.data_ptr(), self.B, self.records.data_ptr(), s)
         self.solver.solve_warm_device(self.records.data_ptr(), self.B, self.warm.data_ptr(), self.results.data_ptr(),
                                       0, s)
@@ -42,8 +57,9 @@ class ControlTick:
                              self.torques.data_ptr(), s)
 
     def capture(self):
-        """Record step() as a graph.  Warm slots, counters and torques keep evolving on replay,
-        exactly as with eager steps; capture itself launches nothing."""
+        """Record step() as a graph.  Plan and warm slots, counters and torques keep evolving on replay,
+        exactly as with eager steps; capture itself launches nothing.  The plan parameters and dt are
+        kernel arguments, so the graph keeps the values they had at capture."""
         torch = self.torch
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()

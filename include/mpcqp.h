@@ -240,6 +240,76 @@ int32_t mpcqp_assemble_records_device(int32_t horizon, const double* d_states, i
 int32_t mpcqp_joint_torques_device(const double* d_tq_records, const mpcqp_result* d_grf, int32_t batch,
                                    int32_t* d_counter, double* d_joint_torques, void* stream);
 
+/* ---- upstream leg plan: A1RobotControl::update_plan (A1RobotControl.cpp:148-202), then
+ * generate_swing_legs_ctrl (:204-287), then the terrain adaptation of compute_grf (:335-376 with
+ * compute_walking_surface, :566-582), in that order, per robot and per tick.  The stage produces the
+ * fields the rest of the tick consumes — MPCQP_ST_CONTACTS, MPCQP_ST_EULER_D[1], MPCQP_TQ_FKIN,
+ * MPCQP_TQ_CONTACTS — and keeps the controller's persistent state (gait counters, swing start points,
+ * the 13 moving-window filters) in a caller-owned device slot per robot.                          */
+#define MPCQP_PLAN_CONTACT_WINDOW 60   /* recent_contact_{x,y,z}_filter (A1RobotControl.cpp:54-56) */
+#define MPCQP_PLAN_TERRAIN_WINDOW 100  /* terrain_angle_filter (A1RobotControl.cpp:52)             */
+
+typedef struct mpcqp_plan_params {
+  double default_foot_pos[12];  /* [leg][xyz] (A1CtrlStates.h:45-47: x +-0.17, y +-0.15, z -0.35)      */
+  double kp_foot[12];           /* [leg][xyz] 300, 400, 400 (A1CtrlStates.h:105-116)                  */
+  double kd_foot[12];           /* [leg][xyz] 8, 8, 8 (A1CtrlStates.h:109-120)                        */
+  double gait_counter_speed[4]; /* 2, 2, 2, 2 (A1CtrlStates.h:103)                                    */
+  double gait_counter_init[4];  /* gait_counter_reset(): 0, 120, 120, 0 (A1CtrlStates.h:323-327)      */
+  double counter_per_gait;      /* 240 (A1CtrlStates.h:24)                                            */
+  double counter_per_swing;     /* 120 (A1CtrlStates.h:25)                                            */
+  double control_dt;            /* MAIN_UPDATE_FREQUENCY / 1000 = 0.0005 (A1CtrlStates.h:333)         */
+  double foot_force_low;        /* FOOT_FORCE_LOW 30 (A1Params.h:38)                                  */
+  double foot_delta_x_limit;    /* FOOT_DELTA_X_LIMIT 0.1 (A1Params.h:44)                             */
+  double foot_delta_y_limit;    /* FOOT_DELTA_Y_LIMIT 0.1 (A1Params.h:45)                             */
+  double swing_clearance1;      /* (double)0.0f, FOOT_SWING_CLEARANCE1 (A1Params.h:41)                */
+  double swing_clearance2;      /* (double)0.4f = 0.4000000059604645, FOOT_SWING_CLEARANCE2 (:42)     */
+  int32_t terrain;              /* stance_leg_control_type == 1 (A1CtrlStates.h:21): fit the terrain  */
+  int32_t use_terrain_adapt;    /* 1 (A1CtrlStates.h:22): write root_euler_d[1]                       */
+} mpcqp_plan_params;
+
+/* Fill *p with A1CtrlStates::reset() (A1CtrlStates.h:20-122) and the A1Params.h:38-45 constants. */
+void mpcqp_plan_default_params(mpcqp_plan_params* p);
+
+/* Per-tick plan input row: the fields of the controller state the MPCQP_ST_* row lacks.           */
+#define MPCQP_PL_ROT_Z 0          /* [9] root_rot_mat_z (yaw-only rotation), row-major               */
+#define MPCQP_PL_FOOT_FORCE 9     /* [4] foot_force (contact sensor, :265)                            */
+#define MPCQP_PL_MOVEMENT_MODE 13 /* movement_mode as 0.0 (standstill) / 1.0 (walk) (:150)            */
+#define MPCQP_PL_SIZE 16          /* 14 used, padded to a multiple of 4 doubles                       */
+
+/* Optional per-robot output row ([leg][xyz] where 12 wide, flags as 0.0 / 1.0).                   */
+#define MPCQP_PO_TARGET_REL 0     /* [4][3] foot_pos_target_rel (:172-197)                            */
+#define MPCQP_PO_TARGET_ABS 12    /* [4][3] foot_pos_target_abs (:199)                                */
+#define MPCQP_PO_TARGET_WORLD 24  /* [4][3] foot_pos_target_world (:200)                              */
+#define MPCQP_PO_FOOT_CUR 36      /* [4][3] foot_pos_cur (:224)                                       */
+#define MPCQP_PO_BEZIER 48        /* [4][3] foot_pos_target, the Bezier point (:238)                  */
+#define MPCQP_PO_FKIN 60          /* [4][3] foot_forces_kin (:251)                                    */
+#define MPCQP_PO_RECENT 72        /* [4][3] foot_pos_recent_contact (:277-280)                        */
+#define MPCQP_PO_GAIT 84          /* [4] gait_counter                                                 */
+#define MPCQP_PO_PLAN 88          /* [4] plan_contacts                                                */
+#define MPCQP_PO_EARLY 92         /* [4] early_contacts                                               */
+#define MPCQP_PO_CONTACTS 96      /* [4] contacts                                                     */
+#define MPCQP_PO_PLANE 100        /* [3] a of compute_walking_surface (:578); 0 with terrain off      */
+#define MPCQP_PO_COS 103          /* angle_cos of cal_dihedral_angle, unfiltered (Utils.cpp:57-60)    */
+#define MPCQP_PO_ANGLE 104        /* terrain_pitch_angle (:375): filtered and clamped                 */
+#define MPCQP_PO_SIZE 108         /* 105 used, padded to a multiple of 4 doubles                      */
+
+/* Doubles per robot of the plan slot, a caller-owned DEVICE buffer d_plan_state [batch][size] that
+ * must follow its robot from tick to tick.  Zero-filled = a freshly reset() controller (the first
+ * tick loads gait_counter from gait_counter_init), the convention of the warm-start slots. */
+int32_t mpcqp_plan_state_size(void);
+
+/* One plan tick for `batch` robots (DEVICE pointers, async on `stream`, no allocation and no
+ * synchronization: hipGraph-capture safe).  Chain it before mpcqp_assemble_records_device on the
+ * same stream.  `dt` is the argument of update_plan / generate_swing_legs_ctrl (the foot velocities
+ * divide by it).  Reads d_states [batch][MPCQP_ST_SIZE] and d_plan_in [batch][MPCQP_PL_SIZE];
+ * writes, in place, MPCQP_ST_CONTACTS and (terrain and use_terrain_adapt set) MPCQP_ST_EULER_D + 1
+ * of d_states, MPCQP_TQ_FKIN and MPCQP_TQ_CONTACTS of d_tq_records [batch][MPCQP_TQ_SIZE] (NULL:
+ * skipped), the slot, and d_plan_out [batch][MPCQP_PO_SIZE] (NULL: skipped).  The reference runs
+ * compute_grf on a thread of its own at the same 0.5 ms period; here it is the same tick. */
+int32_t mpcqp_leg_plan_device(const mpcqp_plan_params* pp, double dt, double* d_states, const double* d_plan_in,
+                              int32_t batch, double* d_plan_state, double* d_tq_records, double* d_plan_out,
+                              void* stream);
+
 /* ---- single-step QP balance controller: the stance_leg_control_type == 0 branch of
  * A1RobotControl::compute_grf (A1RobotControl.cpp:321-332 euler error, :377-444 QP), constants
  * from the A1RobotControl ctor (:7-48).  12 variables (world-frame GRF), 20 rows (4 fz bounds,
