@@ -561,6 +561,52 @@ int32_t mpcqp_leg_plan_device(const mpcqp_plan_params* pp, double dt, double* d_
              : MPCQP_ERR_HIP;
 }
 
+void mpcqp_est_default_params(mpcqp_est_params* p) {
+  if (!p) return;
+  const double ox[4] = {0.1881, 0.1881, -0.1881, -0.1881};    // GazeboA1ROS.cpp:76-79
+  const double oy[4] = {0.04675, -0.04675, 0.04675, -0.04675};  // :80-83
+  const double mo[4] = {0.08, -0.08, 0.08, -0.08};            // :84-87
+  for (int i = 0; i < 4; ++i) {
+    p->rho_fix[i][0] = ox[i];
+    p->rho_fix[i][1] = oy[i];
+    p->rho_fix[i][2] = mo[i];
+    p->rho_fix[i][3] = 0.213;  // :88
+    p->rho_fix[i][4] = 0.213;  // :89
+    for (int k = 0; k < 3; ++k) p->rho_opt[i][k] = 0.0;  // :95
+  }
+  p->process_noise_pimu = 0.01;           // A1BasicEKF.h:16
+  p->process_noise_vimu = 0.01;           // :17
+  p->process_noise_pfoot = 0.01;          // :18
+  p->sensor_noise_pimu_rel_foot = 0.001;  // :19
+  p->sensor_noise_vimu_rel_foot = 0.1;    // :20
+  p->sensor_noise_zfoot = 0.001;          // :21
+  p->height_noise_no_flat = 1e5;          // A1BasicEKF.cpp:51
+  p->init_height = 0.09;                  // :63
+  p->init_cov = 3.0;                      // :59
+  p->gravity = 9.81;                      // :76
+  p->contact_force_scale = 100.0;         // :83
+  p->drift_threshold = 1e-6;              // :143
+  p->drift_divisor = 10.0;                // :146
+  p->assume_flat_ground = 1;              // :40
+  p->pad_ = 0;
+}
+
+int32_t mpcqp_est_params_size(void) { return (int32_t)sizeof(mpcqp_est_params); }
+
+int32_t mpcqp_estimator_state_size(void) { return mpcqp::estimator_state_doubles(); }
+
+int32_t mpcqp_state_estimate_device(const mpcqp_est_params* pp, double dt, const double* d_sensors,
+                                    double* d_plan_in, double* d_states, int32_t batch, double* d_est_state,
+                                    double* d_tq_records, double* d_est_out, void* stream) {
+  if (!pp || batch < 0 || !(dt > 0.0) || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_sensors || !d_plan_in || !d_states || !d_est_state)) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_state_estimate(*pp, dt, d_sensors, d_plan_in, d_states, batch, d_est_state, d_tq_records,
+                                      d_est_out, stream) == hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
 void mpcqp_balance_default_params(mpcqp_balance_params* p) {
   if (!p) return;
   const double q[6] = {1.0, 1.0, 1.0, 400.0, 400.0, 100.0};  // A1RobotControl.cpp:11

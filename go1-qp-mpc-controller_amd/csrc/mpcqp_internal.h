@@ -71,6 +71,11 @@ hipError_t launch_leg_plan(const mpcqp_plan_params& pp, double dt, double* state
                            double* slots, double* tq, double* out, void* stream);
 int plan_state_doubles();  // doubles per robot of the plan slot
 
+// State front end: frames, leg kinematics, Kalman estimator (mpcqp_estimate.hip)
+hipError_t launch_state_estimate(const mpcqp_est_params& pp, double dt, const double* sensors, double* plan_in,
+                                 double* states, int batch, double* slots, double* tq, double* out, void* stream);
+int estimator_state_doubles();  // doubles per robot of the estimator slot
+
 // Single-step QP balance controller (mpcqp_balance.hip)
 hipError_t launch_balance(const mpcqp_balance_params& bp, const mpcqp_params& p, const double* recs, int batch,
                           mpcqp_result* out, void* stream);

@@ -6,6 +6,8 @@ include/mpcqp.h); this package only packs records, owns handles and calls the AB
 from . import _lib
 from ._lib import (assemble_records_device, EXPORTED, LIB_PATH, RESULT_DTYPE, MpcQpError, Params, Result, default_params,
                    load, rec_feet, rec_size, status_str)
+from .estimator import (EST_OUT_DTYPE, EstimatorParams, default_estimator_params, estimator_state_size,
+                        pack_estimator_slot, pack_sensors, state_estimate_device, unpack_estimator_slot)
 from .legplan import (PLAN_OUT_DTYPE, PlanParams, default_plan_params, leg_plan_device, pack_plan_inputs,
                       plan_state_size)
 from .records import (GO1_Q, GO1_R, RobotStates, assemble_compute_grf, assemble_test_mpc,
@@ -20,4 +22,6 @@ __all__ = [
     "assemble_test_mpc", "synthetic_go1", "Go1RobotControl", "RobotControl", "MpcQpSolver",
     "assemble_torque_records", "joint_torques_device", "pack_states", "assemble_records_device",
     "PLAN_OUT_DTYPE", "PlanParams", "default_plan_params", "leg_plan_device", "pack_plan_inputs", "plan_state_size",
+    "EST_OUT_DTYPE", "EstimatorParams", "default_estimator_params", "estimator_state_size", "pack_estimator_slot",
+    "pack_sensors", "state_estimate_device", "unpack_estimator_slot",
 ]

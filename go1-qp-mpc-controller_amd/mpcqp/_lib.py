@@ -37,6 +37,10 @@ TQ_JFOOT, TQ_FKIN, TQ_KM, TQ_GRAV, TQ_CONTACTS, TQ_SIZE = 0, 36, 48, 51, 63, 68
 PL_ROT_Z, PL_FOOT_FORCE, PL_MOVEMENT_MODE, PL_SIZE = 0, 9, 13, 16
 PO_SIZE = 108
 PLAN_CONTACT_WINDOW, PLAN_TERRAIN_WINDOW = 60, 100
+# state front end: sensor row and optional output row (include/mpcqp.h MPCQP_SN_*, MPCQP_EO_*)
+SN_QUAT, SN_JOINT_POS, SN_JOINT_VEL, SN_IMU_ACC, SN_IMU_ANG_VEL, SN_SIZE = 0, 4, 16, 28, 31, 36
+EO_FOOT_POS_REL, EO_FOOT_VEL_REL, EO_FOOT_VEL_ABS, EO_CONTACT_W, EO_X, EO_DIAG_P, EO_DET = 0, 12, 24, 36, 40, 58, 76
+EO_SIZE = 80
 
 
 def rec_feet(N):
@@ -96,6 +100,19 @@ class PlanParams(ctypes.Structure):
     ]
 
 
+class EstimatorParams(ctypes.Structure):
+    """mpcqp_est_params."""
+    _fields_ = [
+        ("rho_fix", ctypes.c_double * 20), ("rho_opt", ctypes.c_double * 12),
+        ("process_noise_pimu", ctypes.c_double), ("process_noise_vimu", ctypes.c_double),
+        ("process_noise_pfoot", ctypes.c_double), ("sensor_noise_pimu_rel_foot", ctypes.c_double),
+        ("sensor_noise_vimu_rel_foot", ctypes.c_double), ("sensor_noise_zfoot", ctypes.c_double),
+        ("height_noise_no_flat", ctypes.c_double), ("init_height", ctypes.c_double), ("init_cov", ctypes.c_double),
+        ("gravity", ctypes.c_double), ("contact_force_scale", ctypes.c_double), ("drift_threshold", ctypes.c_double),
+        ("drift_divisor", ctypes.c_double), ("assume_flat_ground", ctypes.c_int32), ("pad_", ctypes.c_int32),
+    ]
+
+
 class Result(ctypes.Structure):
     """mpcqp_result."""
     _fields_ = [
@@ -127,6 +144,8 @@ EXPORTED = [
     "mpcqp_handoff_counts",
     "mpcqp_debug_set_split", "mpcqp_debug_split_parts",
     "mpcqp_plan_default_params", "mpcqp_plan_state_size", "mpcqp_leg_plan_device",
+    "mpcqp_est_default_params", "mpcqp_est_params_size", "mpcqp_estimator_state_size",
+    "mpcqp_state_estimate_device",
 ]
 
 _libs = {}
@@ -214,6 +233,18 @@ def load(debug=False):
     L.mpcqp_plan_state_size.restype = i32
     L.mpcqp_leg_plan_device.argtypes = [ctypes.POINTER(PlanParams), ctypes.c_double, vp, vp, i32, vp, vp, vp, vp]
     L.mpcqp_leg_plan_device.restype = i32
+    L.mpcqp_est_default_params.argtypes = [ctypes.POINTER(EstimatorParams)]
+    L.mpcqp_est_default_params.restype = None
+    L.mpcqp_est_params_size.argtypes = []
+    L.mpcqp_est_params_size.restype = i32
+    L.mpcqp_estimator_state_size.argtypes = []
+    L.mpcqp_estimator_state_size.restype = i32
+    L.mpcqp_state_estimate_device.argtypes = [ctypes.POINTER(EstimatorParams), ctypes.c_double, vp, vp, vp, i32, vp,
+                                              vp, vp, vp]
+    L.mpcqp_state_estimate_device.restype = i32
+    if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
+        raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
+                         f"{ctypes.sizeof(EstimatorParams)} in ctypes")
     ps, rs = i32(0), i32(0)
     L.mpcqp_abi_sizes(ctypes.byref(ps), ctypes.byref(rs))
     if ps.value != ctypes.sizeof(Params) or rs.value != ctypes.sizeof(Result):

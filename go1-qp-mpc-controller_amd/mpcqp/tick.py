@@ -11,16 +11,24 @@ torch is used only to own device buffers and the capture stream.
 With ``plan`` (a PlanParams) the tick starts one stage earlier, with the leg plan (update_plan,
 generate_swing_legs_ctrl and the terrain adaptation of compute_grf, A1RobotControl.cpp:148-287,
 :335-376): it fills the contacts, the swing-leg force and root_euler_d[1] of ``states`` /
-``tq_records`` on the device from ``plan_in``, so the caller writes only sensor-level state.
+``tq_records`` on the device from ``plan_in``.
+
+With ``estimator`` (an EstimatorParams) it starts another stage earlier, with the state front end (pose
+and IMU callbacks, GazeboA1ROS.cpp:242-307, and A1BasicEKF::update_estimation, A1BasicEKF.cpp:55-164):
+root_euler, root_pos, root_ang_vel, root_lin_vel, root_rot_mat and foot_pos_abs of ``states``,
+root_rot_mat_z of ``plan_in`` and j_foot of ``tq_records`` are computed on the device from ``sensors``
+(quaternion, joint angles and rates, IMU sample) and the foot forces of ``plan_in``, so the caller writes
+only sensor-level state.  The estimator runs first: the plan and the solve see this tick's estimate.
 """
 from . import _lib
+from .estimator import estimator_state_size, state_estimate_device
 from .legplan import leg_plan_device, plan_state_size
 from .solver import MpcQpSolver
 from .torques import joint_torques_device
 
 
 class ControlTick:
-    def __init__(self, batch, params=None, device=0, plan=None, dt=None):
+    def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None):
         import torch
         self.torch = torch
         self.B = int(batch)
@@ -42,11 +50,25 @@ class ControlTick:
             self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)   # caller writes rot_z / foot_force / mode
             self.plan_state = torch.zeros((self.B, plan_state_size()), **f64)  # zero = reset() controller
             self.plan_out = torch.zeros((self.B, _lib.PO_SIZE), **f64)
+        self.estimator = estimator
+        if estimator is not None:
+            if plan is None:
+                if dt is None:
+                    raise ValueError("ControlTick(estimator=...) without plan= needs dt")
+                self.dt = float(dt)  # update_estimation's dt argument
+                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # caller writes foot_force / mode
+            self.sensors = torch.zeros((self.B, _lib.SN_SIZE), **f64)    # caller writes quat / joints / IMU here
+            self.est_state = torch.zeros((self.B, estimator_state_size()), **f64)  # zero = not initialized
+            self.est_out = torch.zeros((self.B, _lib.EO_SIZE), **f64)
         self.graph = None
 
     def step(self, stream=None):
         """Enqueue one tick on `stream` (default: torch's current stream)."""
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        if self.estimator is not None:
+            state_estimate_device(self.estimator, self.dt, self.sensors.data_ptr(), self.plan_in.data_ptr(),
+                                  self.states.data_ptr(), self.B, self.est_state.data_ptr(),
+                                  self.tq_records.data_ptr(), self.est_out.data_ptr(), s)
         if self.plan is not None:
             leg_plan_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
                             self.plan_state.data_ptr(), self.tq_records.data_ptr(), self.plan_out.data_ptr(), s)
@@ -57,8 +79,8 @@ class ControlTick:
                              self.torques.data_ptr(), s)
 
     def capture(self):
-        """Record step() as a graph.  Plan and warm slots, counters and torques keep evolving on replay,
-        exactly as with eager steps; capture itself launches nothing.  The plan parameters and dt are
+        """Record step() as a graph.  Estimator, plan and warm slots, counters and torques keep evolving on replay,
+        exactly as with eager steps; capture itself launches nothing.  The estimator and plan parameters and dt are
         kernel arguments, so the graph keeps the values they had at capture."""
         torch = self.torch
         torch.cuda.synchronize()

@@ -310,6 +310,83 @@ int32_t mpcqp_leg_plan_device(const mpcqp_plan_params* pp, double dt, double* d_
                               int32_t batch, double* d_plan_state, double* d_tq_records, double* d_plan_out,
                               void* stream);
 
+/* ---- state front end: what the reference computes between the sensor callbacks and the plan,
+ *   pose callback   src/a1_cpp/src/GazeboA1ROS.cpp:242-289 (root_rot_mat, root_euler, root_rot_mat_z:
+ *                   :265-269 with Utils::quat_to_euler, utils/Utils.cpp:7-33; leg forward kinematics,
+ *                   Jacobian, foot positions and velocities: :272-285, legKinematics/A1Kinematics.cpp:39-130)
+ *   IMU callback    GazeboA1ROS.cpp:291-307 (root_ang_vel = root_rot_mat * imu_ang_vel, :306)
+ *   A1BasicEKF      init_state / update_estimation, src/a1_cpp/src/A1BasicEKF.cpp:55-164 (18 states,
+ *                   28 measurements; root_pos and root_lin_vel are its outputs, :162-163)
+ * per robot and per tick, in that order.  The stage runs FIRST in the tick, so the plan and the solve of
+ * a tick see that tick's estimate (the reference runs the estimator after the plan inside main_update,
+ * GazeboA1ROS.cpp:190-198, while compute_grf reads whatever is latest from its own thread).
+ *
+ * Sensor row, one per robot (offsets in doubles).  The IMU callback's five-sample moving averages
+ * (GazeboA1ROS.cpp:296-305) run at sensor rate outside the tick: the row holds the filtered values.
+ * foot_force and movement_mode are read from the MPCQP_PL_* row.                                  */
+#define MPCQP_SN_QUAT 0          /* [4] root_quat as w, x, y, z (GazeboA1ROS.cpp:244-247)             */
+#define MPCQP_SN_JOINT_POS 4     /* [12] joint_pos, FL FR RL RR x (hip, thigh, calf) (:310-318)       */
+#define MPCQP_SN_JOINT_VEL 16    /* [12] joint_vel                                                    */
+#define MPCQP_SN_IMU_ACC 28      /* [3] imu_acc, body frame (:296-300)                                */
+#define MPCQP_SN_IMU_ANG_VEL 31  /* [3] imu_ang_vel, body frame (:301-305)                            */
+#define MPCQP_SN_SIZE 36         /* 34 used, padded to a multiple of 4 doubles                        */
+
+typedef struct mpcqp_est_params {
+  double rho_fix[4][5];  /* per leg: hip offset x, y, motor offset, upper, lower link (GazeboA1ROS.cpp:76-93) */
+  double rho_opt[4][3];  /* per leg: calibration offsets, 0 (GazeboA1ROS.cpp:94-95)                       */
+  double process_noise_pimu;         /* PROCESS_NOISE_PIMU 0.01 (A1BasicEKF.h:16)                        */
+  double process_noise_vimu;         /* PROCESS_NOISE_VIMU 0.01 (A1BasicEKF.h:17)                        */
+  double process_noise_pfoot;        /* PROCESS_NOISE_PFOOT 0.01 (A1BasicEKF.h:18)                       */
+  double sensor_noise_pimu_rel_foot; /* SENSOR_NOISE_PIMU_REL_FOOT 0.001 (A1BasicEKF.h:19)               */
+  double sensor_noise_vimu_rel_foot; /* SENSOR_NOISE_VIMU_REL_FOOT 0.1 (A1BasicEKF.h:20)                 */
+  double sensor_noise_zfoot;         /* SENSOR_NOISE_ZFOOT 0.001 (A1BasicEKF.h:21)                       */
+  double height_noise_no_flat;       /* 1e5: R of the height rows without flat ground (A1BasicEKF.cpp:51) */
+  double init_height;                /* 0.09 (A1BasicEKF.cpp:63)                                         */
+  double init_cov;                   /* 3 (A1BasicEKF.cpp:59)                                            */
+  double gravity;                    /* 9.81 (A1BasicEKF.cpp:76)                                         */
+  double contact_force_scale;        /* 100 (A1BasicEKF.cpp:83)                                          */
+  double drift_threshold;            /* 1e-6 (A1BasicEKF.cpp:143)                                        */
+  double drift_divisor;              /* 10 (A1BasicEKF.cpp:146)                                          */
+  int32_t assume_flat_ground;        /* 1 (A1BasicEKF.cpp:40)                                            */
+  int32_t pad_;
+} mpcqp_est_params;
+
+/* Fill *p from GazeboA1ROS.cpp:72-98 (A1 leg geometry) and A1BasicEKF.h:16-21 / A1BasicEKF.cpp:40-63. */
+void mpcqp_est_default_params(mpcqp_est_params* p);
+int32_t mpcqp_est_params_size(void); /* sizeof(mpcqp_est_params), for bindings                          */
+
+/* Optional per-robot output row ([leg][xyz] where 12 wide).                                          */
+#define MPCQP_EO_FOOT_POS_REL 0   /* [4][3] foot_pos_rel (GazeboA1ROS.cpp:273)                         */
+#define MPCQP_EO_FOOT_VEL_REL 12  /* [4][3] foot_vel_rel (:281)                                        */
+#define MPCQP_EO_FOOT_VEL_ABS 24  /* [4][3] foot_vel_abs (:284)                                        */
+#define MPCQP_EO_CONTACT_W 36     /* [4] estimated_contacts, continuous (A1BasicEKF.cpp:79-86); the
+                                     thresholded flags (:151-157) are CONTACT_W >= 0.5; 0 on the first tick */
+#define MPCQP_EO_X 40             /* [18] x after the tick                                             */
+#define MPCQP_EO_DIAG_P 58        /* [18] diagonal of P after the tick                                 */
+#define MPCQP_EO_DET 76           /* det P[0:2,0:2] as tested before the reset (:143); 0 on the first tick */
+#define MPCQP_EO_SIZE 80          /* 77 used, padded to a multiple of 4 doubles                        */
+
+/* Doubles per robot of the estimator slot, a caller-owned DEVICE buffer d_est_state [batch][size] that
+ * must follow its robot from tick to tick: the init flag, x and P of A1BasicEKF (A1BasicEKF.h:33-38).
+ * Zero-filled = is_inited() == false, the convention of the warm-start and plan slots. */
+int32_t mpcqp_estimator_state_size(void);
+
+/* One front-end tick for `batch` robots (DEVICE pointers, async on `stream`, no allocation and no
+ * synchronization: hipGraph-capture safe).  Chain it before mpcqp_leg_plan_device on the same stream.
+ * `dt` is update_estimation's argument.  Reads d_sensors [batch][MPCQP_SN_SIZE] and MPCQP_PL_FOOT_FORCE /
+ * MPCQP_PL_MOVEMENT_MODE of d_plan_in [batch][MPCQP_PL_SIZE]; writes, in place, MPCQP_ST_EULER, _POS,
+ * _ANG_VEL, _LIN_VEL, _ROT and _FEET of d_states [batch][MPCQP_ST_SIZE], MPCQP_PL_ROT_Z of d_plan_in,
+ * MPCQP_TQ_JFOOT of d_tq_records [batch][MPCQP_TQ_SIZE] (NULL: skipped), the slot, and d_est_out
+ * [batch][MPCQP_EO_SIZE] (NULL: skipped); nothing else.  A robot's first tick (zero slot) runs init_state
+ * only and leaves MPCQP_ST_POS / _LIN_VEL as the caller wrote them (A1BasicEKF.cpp:55-68 does not touch
+ * state.root_pos).  The innovation covariance S = C Pbar C' + R is factored without pivoting (LDL'; the
+ * reference: fullPivHouseholderQr, :134-138).  A robot whose sensor row is non-finite, or whose
+ * factorization meets a pivot that is not positive and finite, keeps its slot untouched and gets NaN in
+ * MPCQP_ST_POS / _LIN_VEL, so the solve reports MPCQP_STATUS_NAN_INPUT for that robot alone. */
+int32_t mpcqp_state_estimate_device(const mpcqp_est_params* pp, double dt, const double* d_sensors,
+                                    double* d_plan_in, double* d_states, int32_t batch, double* d_est_state,
+                                    double* d_tq_records, double* d_est_out, void* stream);
+
 /* ---- single-step QP balance controller: the stance_leg_control_type == 0 branch of
  * A1RobotControl::compute_grf (A1RobotControl.cpp:321-332 euler error, :377-444 QP), constants
  * from the A1RobotControl ctor (:7-48).  12 variables (world-frame GRF), 20 rows (4 fz bounds,
