@@ -19,7 +19,7 @@ struct LaunchArgs {
   int trace_cap;
   double* wstate;  // warm-start slots [batch][warm_state_doubles(N)] (wave path) or nullptr
   int* fallback;   // wave path: 4 hand-off counters (handle-owned): [0] rank-deficient feet,
-                   // [2] ill-conditioned Schur core after a rho update ([1], [3] unused)
+                   // [1] S_max * amp > SCHUR_AMP, [2] S_max > SCHUR_SMAX, [3] unused
   int grid;
   void* stream;
   mpcqp_params p;
@@ -28,13 +28,18 @@ struct LaunchArgs {
 // Formulation only (mpcqp_build.hip): ConvexMpc::calculate_qp_mats, horizons 1..20
 hipError_t launch_build_any(const LaunchArgs& a, double* P, double* q, double* l, double* u);
 
-// The solve: scale_kernel + one-wave-per-robot Riccati wave_kernel (mpcqp_wave.hip), horizons
-// 1..WAVE_MAX_HORIZON
+// The solve: scale_kernel (mpcqp_scale.hip), then the one-wave-per-robot wave_kernel
+// (mpcqp_wave.hip), horizons 1..WAVE_MAX_HORIZON
 hipError_t launch_wave_any(const LaunchArgs& a);
 hipError_t occupancy_wave_any(const mpcqp_params& p, int* blocks);
 hipError_t wave_selftest(double* d_out, void* stream);
 hipError_t launch_scale_any(const LaunchArgs& a);  // scale_kernel alone (the image in a.work)
 constexpr int WAVE_MAX_HORIZON = 20;
+// the horizons both files instantiate their kernels for (static ISA tools build a single one)
+#ifndef MPCQP_WAVE_FOR_EACH_N
+#define MPCQP_WAVE_FOR_EACH_N(X) \
+  X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20)
+#endif
 
 #ifdef MPCQP_DEBUG_PATHS
 // Cross-check solvers, built only into libmpcqp_debug.so (mpcqp_debug_set_solver 1, 2):
@@ -48,12 +53,12 @@ hipError_t occupancy_riccati_any(int horizon, int* blocks);
 size_t riccati_workspace_doubles(int horizon);  // per robot
 #endif
 constexpr int DENSE_MAX_HORIZON = 10;
-// doubles per robot of the warm-start slot (mpcqp_wave.hip WarmLayout)
+// doubles per robot of the warm-start slot (mpcqp_wave_common.h WarmLayout)
 __host__ __device__ constexpr int warm_state_doubles(int N) {
   return 4 + 3 * 12 * N + 5 * 20 * N + ((12 * N + 63) / 64) * 12 * N;
 }
 
-// doubles per robot of the scaling image scale_kernel hands to wave_kernel (mpcqp_wave.hip ScaleImg)
+// doubles per robot of the scaling image scale_kernel hands to wave_kernel (mpcqp_wave_common.h ScaleImg)
 __host__ __device__ constexpr int scale_image_doubles(int N) { return 3 * 12 * N + 20 * N + 3; }
 
 // Downstream torque map (mpcqp_torque.hip)

@@ -265,14 +265,13 @@ struct GjCols {
 // the other columns' FMAs.  issue(IC<p>) runs at pivot p (the caller's matrix-core work).
 template <int PV, class Issue>
 __device__ __forceinline__ void gj_rows(double (&R)[16], int li, Issue&& issue) {
-  const double one = 1.0;
   struct Pv {
     double g, newc;
   };
   auto prelude = [&](auto P) __attribute__((always_inline)) {
     constexpr int p = decltype(P)::value;
     Pv o;
-    const double pinv = recip(rbcast<p>(R[p], one));
+    const double pinv = recip(rbcast<p>(R[p]));
     const double cp = R[p] * pinv;
     o.g = li == p ? pinv - 1.0 : -cp;
     o.newc = li == p ? pinv : -cp;
@@ -491,13 +490,9 @@ __device__ __forceinline__ void schur_gj_mfma(const double (&S)[64], SchurLds<N>
 #pragma unroll
       for (int m = 16 * NB; m < QS; m += 2) *reinterpret_cast<double2*>(&F.Q[QS * t + m]) = make_double2(0.0, 0.0);
   }
-#ifdef MPCQP_GJ_STORE_SEL
-  // branch-free stores: an entry outside Q (pad rows / columns) goes to the lane's own slot of qv,
-  // which the KKT solve and P~x write before they read it.  0.9k cycles less per factorization in
-  // tools/mb/mb_gjsweep, but C2 / C5 unchanged within noise in the product (profiles/r06/gj_mfma/
-  // store_ab.txt): off
-  double* const dummy = &F.qv[t];
-#endif
+  // (branch-free stores, with entries outside Q sent to a dummy slot: 0.9k cycles less per
+  // factorization in tools/mb/mb_gjsweep, C2 / C5 unchanged within noise in the product,
+  // profiles/r06/gj_mfma/store_ab.txt: not kept)
 #pragma unroll
   for (int I = 0; I < NB; ++I)
 #pragma unroll
@@ -506,13 +501,8 @@ __device__ __forceinline__ void schur_gj_mfma(const double (&S)[64], SchurLds<N>
       for (int v = 0; v < 4; ++v) {
         const int r = 16 * I + 4 * v + grp, c = 16 * J + j;
         const double x = ((I == J && j == 4 * v + grp) ? 1.0 : 0.0) - X[I][J][v];
-#ifdef MPCQP_GJ_STORE_SEL
-        *(r < NI && c < QS ? &F.Q[QS * r + c] : dummy) = x;
-        if (I != J) *(c < NI && r < QS ? &F.Q[QS * c + r] : dummy) = x;
-#else
         if (r < NI && c < QS) F.Q[QS * r + c] = x;
         if (I != J && c < NI && r < QS) F.Q[QS * c + r] = x;
-#endif
       }
 #else
   {  // keep the sweep's results live
@@ -628,10 +618,6 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
   const bool iv = t < NI;
   const int k = i / 6, c = i % 6;
   mark(25);  // entry (the R' blocks are in LDS)
-#ifdef MPCQP_REPEAT_PROLOGUE  // cost measurement builds: the (idempotent) prologue runs twice
-  double vw[12];
-  for (int rep = 0; rep < 2; ++rep) {
-#endif
   // R'^-1 per foot (cofactor inverse of the symmetric 3x3): the variable lane's row a
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -748,9 +734,7 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
     bl[j] = s;
   }
   // columns of sqrt(c) Qv^1/2 L_k and sqrt(c) Qp^1/2 Ac6 L_k (Ac6 = A[0:6, 6:12])
-#ifndef MPCQP_REPEAT_PROLOGUE
   double vw[12];
-#endif
 #pragma unroll
   for (int e = 0; e < 6; ++e) vw[e] = sqrt(cost_c * (2.0 * p.q_weights[6 + e])) * Lc[e];
 #pragma unroll
@@ -768,10 +752,6 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
   // pad lanes: zero columns (their rows of S stay 0; nothing reads their broadcasts)
 #pragma unroll
   for (int e = 0; e < 12; ++e) vw[e] = iv ? vw[e] : 0.0;
-#ifdef MPCQP_REPEAT_PROLOGUE
-  wave_sync();
-  }
-#endif
   {
     double sv = 0.0, sw = 0.0;
 #pragma unroll
@@ -819,8 +799,11 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
   mark(14);
 #if MPCQP_GJ_MFMA
   // internal marks: cycle counts kept in registers, recorded after the sweep (no branch inside it)
-  long long gts[12];
-  int gid[12], ng = 0;
+  // (the sweep stamps 60 and 61, then 62, 63, 64 per block row, without 63 in the last)
+  constexpr int NB = (NI + 15) / 16, NG = 3 * NB + 1;
+  static_assert(NG == 2 + 3 * (NB - 1) + 2, "one slot per mark of schur_gj_mfma");
+  long long gts[NG];
+  int gid[NG], ng = 0;
   auto stamp = [&](int id) __attribute__((always_inline)) {
 #ifdef MPCQP_PHASE_TIMING
     gid[ng] = id;

@@ -1,7 +1,7 @@
-// mpcqp_wave_common.h — device pieces shared by the one-wave (mpcqp_wave.hip) and the
-// wave-per-round (mpcqp_wave_mw.hip) solve kernels: lane layout, cross-lane mat-vecs, the
-// discrete dynamics, the MFMA Riccati factorization, and the scale_kernel image layout.
-// Not installed.
+// mpcqp_wave_common.h — device pieces shared by the solve kernel (mpcqp_wave.hip, mpcqp_schur.h)
+// and the scaling kernel before it (mpcqp_scale.hip): lane layout, cross-lane mat-vecs, the
+// discrete dynamics, the MFMA Riccati factorization, H's columns (gen_col) and the scale_kernel
+// image layout.  Not installed.
 #pragma once
 #include <type_traits>
 
@@ -49,9 +49,7 @@ struct SchurLds;
 // matrices Acl_k = A - B_k K_k are stored for the chains; without (long horizons: the three factor
 // families would leave room for only two robots per CU) the chains apply A and B_k K_k separately,
 // and the R'_k foot blocks share G_k^-1's slot (read by factorization step k before it writes G_k^-1).
-#ifndef MPCQP_ACL_MAXN
-#define MPCQP_ACL_MAXN 12
-#endif
+constexpr int ACL_MAXN = 12;
 template <int N, bool SACL>
 struct RicFactors;
 template <int N>
@@ -83,7 +81,7 @@ struct RicFactors<N, false> {
 template <int N, int KS>
 struct WSmem {
   using C = Cfg<N>;
-  static constexpr bool SACL = N <= MPCQP_ACL_MAXN;
+  static constexpr bool SACL = N <= ACL_MAXN;
   static constexpr int NK = N > 1 ? N - 1 : 1;  // K_k stored for k = 1..N-1
   static constexpr int NA = N > 2 ? N - 2 : 1;  // Acl_k stored for k = 1..N-2 (SACL)
   alignas(16) double Bw[N][3][ND];  // rows 6-8 of B_d(k) = I_w^-1 skew(foot) dt (rows 9-11: dt/m I)
@@ -94,10 +92,6 @@ struct WSmem {
       double lam[N][ND];  // gradient adjoint lambda_k (states 0..11)
       double vec[2][16];  // sequential 13-vectors (gradient forward sweep)
       double qn[C::n];     // this tick's gradient (warm start: q of the Ruiz passes is the old one)
-      // OSQP scale_data inside the Schur-form wave (scale_wave, KS = 1 only): the Ruiz passes' second
-      // D / E buffers, the unscaled A entries and the raw column norms (inside the union: no LDS added)
-      static constexpr int FX = KS == 1 ? 1 : 0;
-      double Dx[FX ? C::n : 1], Ex[FX ? C::m : 1], Ap[2][FX ? C::m : 1], cm0[FX ? C::n : 1];
     } h;
     // KS = 0: the Riccati factors; KS = 1: the impulse-space Schur form (mpcqp_schur.h)
     typename std::conditional<KS == 0, RicFactors<N, SACL>, SchurLds<N>>::type f;
@@ -112,30 +106,21 @@ struct WSmem {
 // each block that may follow the VALU write of its src0 starts with a wait: WV_NOP_HEAD (2 states).
 // A block whose src0 an earlier block of the same sequence already read (the sources of a sequence are
 // materialized together before its first block) waits for nothing (WV_NOP_INNER).  tools/isa_hazards.py
-// verifies the placement on the compiled product kernels (tests/test_isa_hazards.py); the round-4
-// placement (s_nop 4 / s_nop 1 at every block) remains as MPCQP_NOP_SAFE: C2 1.737 -> 1.677 ms,
-// C4 6.75 -> 6.20 ms, bitwise equal results (profiles/r05/nop_lean).
-#ifndef MPCQP_NOP_SAFE
+// verifies the placement on the compiled product kernels (tests/test_isa_hazards.py).  Against the
+// round-4 placement (s_nop 4 / s_nop 1 at every block): C2 1.737 -> 1.677 ms, C4 6.75 -> 6.20 ms,
+// bitwise equal results (profiles/r05/nop_lean).
 #define WV_NOP_HEAD "s_nop 1\n\t"
 #define WV_NOP_INNER ""
 #define WV_NOP_HEAD1 "s_nop 1\n\t"
 #define WV_NOP_INNER1 ""
 #define WV_NOP_PERM "s_nop 0\n\t"
-#else
-#define WV_NOP_HEAD "s_nop 4\n\t"
-#define WV_NOP_INNER "s_nop 4\n\t"
-#define WV_NOP_HEAD1 "s_nop 1\n\t"
-#define WV_NOP_INNER1 "s_nop 1\n\t"
-#define WV_NOP_PERM "s_nop 1\n\t"
-#endif
 
 // ---- cross-lane primitives ---------------------------------------------------------------------
 #define WV_FM(A, M, L) "v_fmac_f64_dpp " A ", %[x], " M " row_newbcast:" #L " row_mask:0xf bank_mask:0xf\n\t"
-#ifndef MPCQP_MV_MULTI_ACC
 // y_i = sum_c M[i][c] x_c, x_c broadcast from lane 4(c/3)+c%3 of each DPP row, M row i in `c`.
 // One accumulator per mat-vec, the terms in column order: a dependent v_fmac_f64_dpp chain issues as
 // fast as independent ones for a lone wave (4.4 against 5.35 cycles, tools/mb/mb_valu), so rotating
-// accumulators only cost the zeroing moves and the closing adds (the round-4 form: MPCQP_MV_MULTI_ACC).
+// accumulators only cost the zeroing moves and the closing adds (the round-4 form).
 // Each FMA reads the accumulator its predecessor just wrote.  The DPP wait-state requirement (VALU
 // write, then a DPP read of that VGPR: 2 states) concerns the operand read through the lane permute,
 // src0 (here x, written before the block's head wait); the accumulator is an ordinary dependent VALU
@@ -271,124 +256,6 @@ __device__ __forceinline__ void chain_fwd(double m, const double (&kc)[12], cons
 #undef WV_M12
 #undef WV_M6HI
 #undef WV_M6LO
-#else
-// y_i = sum_c M[i][c] x_c, x_c broadcast from lane 4(c/3)+c%3 of each DPP row, M row i in `c`.
-// Hazards (the compiler cannot see into the asm): a DPP instruction needs 2 wait states after a
-// VALU write of ANY of its VGPR operands and 5 after an EXEC write.  Hence the leading s_nop 4 and
-// three accumulators in rotation (each is re-read 3 instructions after it was written).
-__device__ __forceinline__ double mv12(double x, const double (&c)[12]) {
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-  asm(WV_NOP_HEAD
-      WV_FM("%[a0]", "%[c0]", 0) WV_FM("%[a1]", "%[c1]", 1) WV_FM("%[a2]", "%[c2]", 2)
-      WV_FM("%[a0]", "%[c3]", 4) WV_FM("%[a1]", "%[c4]", 5) WV_FM("%[a2]", "%[c5]", 6)
-      WV_FM("%[a0]", "%[c6]", 8) WV_FM("%[a1]", "%[c7]", 9) WV_FM("%[a2]", "%[c8]", 10)
-      WV_FM("%[a0]", "%[c9]", 12) WV_FM("%[a1]", "%[c10]", 13) WV_FM("%[a2]", "%[c11]", 14)
-      : [a0] "+&v"(a0), [a1] "+&v"(a1), [a2] "+&v"(a2)
-      : [x] "v"(x), [c0] "v"(c[0]), [c1] "v"(c[1]), [c2] "v"(c[2]), [c3] "v"(c[3]), [c4] "v"(c[4]),
-        [c5] "v"(c[5]), [c6] "v"(c[6]), [c7] "v"(c[7]), [c8] "v"(c[8]), [c9] "v"(c[9]), [c10] "v"(c[10]),
-        [c11] "v"(c[11]));
-  return (a0 + a1) + a2;
-}
-// sum over states 6..11 (lanes 8, 9, 10, 12, 13, 14) of c[s-6] x_s
-__device__ __forceinline__ double mv6(double x, const double (&c)[6]) {
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-  asm(WV_NOP_HEAD
-      WV_FM("%[a0]", "%[c0]", 8) WV_FM("%[a1]", "%[c1]", 9) WV_FM("%[a2]", "%[c2]", 10)
-      WV_FM("%[a0]", "%[c3]", 12) WV_FM("%[a1]", "%[c4]", 13) WV_FM("%[a2]", "%[c5]", 14)
-      : [a0] "+&v"(a0), [a1] "+&v"(a1), [a2] "+&v"(a2)
-      : [x] "v"(x), [c0] "v"(c[0]), [c1] "v"(c[1]), [c2] "v"(c[2]), [c3] "v"(c[3]), [c4] "v"(c[4]),
-        [c5] "v"(c[5]));
-  return (a0 + a1) + a2;
-}
-// Two / three independent mat-vecs interleaved in one block (each has its own x and rows); every
-// accumulator is re-read 4 (x2) or 6 (x3) instructions after its last write.
-#define WV_T2(L, I, J) WV_FX("%[a" #J "]", "%[x0]", "%[p" #I "]", L) WV_FX("%[b" #J "]", "%[x1]", "%[q" #I "]", L)
-#define WV_T3(L, I, J) WV_T2(L, I, J) WV_FX("%[d" #J "]", "%[x2]", "%[r" #I "]", L)
-#define WV_FX(A, X, M, L) "v_fmac_f64_dpp " A ", " X ", " M " row_newbcast:" #L " row_mask:0xf bank_mask:0xf\n\t"
-#define WV_OPS12(P, C) [P##0] "v"(C[0]), [P##1] "v"(C[1]), [P##2] "v"(C[2]), [P##3] "v"(C[3]), [P##4] "v"(C[4]), \
-    [P##5] "v"(C[5]), [P##6] "v"(C[6]), [P##7] "v"(C[7]), [P##8] "v"(C[8]), [P##9] "v"(C[9]),                \
-    [P##10] "v"(C[10]), [P##11] "v"(C[11])
-__device__ __forceinline__ void mv12x2(double x0, double x1, const double (&c0)[12], const double (&c1)[12],
-                                       double& y0, double& y1) {
-  double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
-  asm(WV_NOP_HEAD
-      WV_T2(0, 0, 0) WV_T2(1, 1, 1) WV_T2(2, 2, 0) WV_T2(4, 3, 1) WV_T2(5, 4, 0) WV_T2(6, 5, 1)
-      WV_T2(8, 6, 0) WV_T2(9, 7, 1) WV_T2(10, 8, 0) WV_T2(12, 9, 1) WV_T2(13, 10, 0) WV_T2(14, 11, 1)
-      : [a0] "+&v"(a0), [a1] "+&v"(a1), [b0] "+&v"(b0), [b1] "+&v"(b1)
-      : [x0] "v"(x0), [x1] "v"(x1), WV_OPS12(p, c0), WV_OPS12(q, c1));
-  y0 = a0 + a1;
-  y1 = b0 + b1;
-}
-__device__ __forceinline__ void mv12x3(double x0, double x1, double x2, const double (&c0)[12],
-                                       const double (&c1)[12], const double (&c2)[12], double& y0, double& y1,
-                                       double& y2) {
-  double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0, d0 = 0.0, d1 = 0.0;
-  asm(WV_NOP_HEAD
-      WV_T3(0, 0, 0) WV_T3(1, 1, 1) WV_T3(2, 2, 0) WV_T3(4, 3, 1) WV_T3(5, 4, 0) WV_T3(6, 5, 1)
-      WV_T3(8, 6, 0) WV_T3(9, 7, 1) WV_T3(10, 8, 0) WV_T3(12, 9, 1) WV_T3(13, 10, 0) WV_T3(14, 11, 1)
-      : [a0] "+&v"(a0), [a1] "+&v"(a1), [b0] "+&v"(b0), [b1] "+&v"(b1), [d0] "+&v"(d0), [d1] "+&v"(d1)
-      : [x0] "v"(x0), [x1] "v"(x1), [x2] "v"(x2), WV_OPS12(p, c0), WV_OPS12(q, c1), WV_OPS12(r, c2));
-  y0 = a0 + a1;
-  y1 = b0 + b1;
-  y2 = d0 + d1;
-}
-#undef WV_T2
-#undef WV_T3
-#undef WV_FX
-#undef WV_OPS12
-// y[r] = M_r x[r] for the R register rounds of a parallel phase, interleaved.
-template <int R>
-__device__ __forceinline__ void mv_rounds(const double (&x)[R], const double (&c)[R][12], double (&y)[R]) {
-  if constexpr (R == 1) {
-    y[0] = mv12(x[0], c[0]);
-  } else if constexpr (R == 2) {
-    mv12x2(x[0], x[1], c[0], c[1], y[0], y[1]);
-  } else if constexpr (R == 3) {
-    mv12x3(x[0], x[1], x[2], c[0], c[1], c[2], y[0], y[1], y[2]);
-  } else {
-#pragma unroll
-    for (int r = 0; r < R; ++r) y[r] = mv12(x[r], c[r]);
-  }
-}
-// init + sum_c M[c] x_c: the chains' "- a_k" / "+ h_k" folded into the first accumulator
-__device__ __forceinline__ double mv12a(double x, const double (&c)[12], double init) {
-  double a0 = init, a1 = 0.0, a2 = 0.0;
-  asm(WV_NOP_HEAD
-      WV_FM("%[a1]", "%[c1]", 1) WV_FM("%[a2]", "%[c2]", 2) WV_FM("%[a0]", "%[c0]", 0)
-      WV_FM("%[a1]", "%[c4]", 5) WV_FM("%[a2]", "%[c5]", 6) WV_FM("%[a0]", "%[c3]", 4)
-      WV_FM("%[a1]", "%[c7]", 9) WV_FM("%[a2]", "%[c8]", 10) WV_FM("%[a0]", "%[c6]", 8)
-      WV_FM("%[a1]", "%[c10]", 13) WV_FM("%[a2]", "%[c11]", 14) WV_FM("%[a0]", "%[c9]", 12)
-      : [a0] "+&v"(a0), [a1] "+&v"(a1), [a2] "+&v"(a2)
-      : [x] "v"(x), [c0] "v"(c[0]), [c1] "v"(c[1]), [c2] "v"(c[2]), [c3] "v"(c[3]), [c4] "v"(c[4]),
-        [c5] "v"(c[5]), [c6] "v"(c[6]), [c7] "v"(c[7]), [c8] "v"(c[8]), [c9] "v"(c[9]), [c10] "v"(c[10]),
-        [c11] "v"(c[11]));
-  return (a1 + a2) + a0;
-}
-
-// init + sum over states 6..11 (lanes 8, 9, 10, 12, 13, 14) of c[s-6] x_s
-__device__ __forceinline__ double mv6a(double x, const double (&c)[6], double init) {
-  double a0 = init, a1 = 0.0, a2 = 0.0;
-  asm(WV_NOP_HEAD
-      WV_FM("%[a1]", "%[c0]", 8) WV_FM("%[a2]", "%[c1]", 9) WV_FM("%[a0]", "%[c2]", 10)
-      WV_FM("%[a1]", "%[c3]", 12) WV_FM("%[a2]", "%[c4]", 13) WV_FM("%[a0]", "%[c5]", 14)
-      : [a0] "+&v"(a0), [a1] "+&v"(a1), [a2] "+&v"(a2)
-      : [x] "v"(x), [c0] "v"(c[0]), [c1] "v"(c[1]), [c2] "v"(c[2]), [c3] "v"(c[3]), [c4] "v"(c[4]),
-        [c5] "v"(c[5]));
-  return (a1 + a2) + a0;
-}
-// init + sum over states 0..5 (lanes 0, 1, 2, 4, 5, 6) of c[s] x_s
-__device__ __forceinline__ double mv6lo_a(double x, const double (&c)[6], double init) {
-  double a0 = init, a1 = 0.0, a2 = 0.0;
-  asm(WV_NOP_HEAD
-      WV_FM("%[a1]", "%[c0]", 0) WV_FM("%[a2]", "%[c1]", 1) WV_FM("%[a0]", "%[c2]", 2)
-      WV_FM("%[a1]", "%[c3]", 4) WV_FM("%[a2]", "%[c4]", 5) WV_FM("%[a0]", "%[c5]", 6)
-      : [a0] "+&v"(a0), [a1] "+&v"(a1), [a2] "+&v"(a2)
-      : [x] "v"(x), [c0] "v"(c[0]), [c1] "v"(c[1]), [c2] "v"(c[2]), [c3] "v"(c[3]), [c4] "v"(c[4]),
-        [c5] "v"(c[5]));
-  return (a1 + a2) + a0;
-}
-
-#endif  // MPCQP_MV_MULTI_ACC
 #undef WV_FM
 
 // quad_perm DPP of a double
@@ -629,20 +496,11 @@ __device__ __forceinline__ double bcast_group(double x) {
   const double w = xor32(z);  // group g ^ 2
   return ((g & 2) == (GP & 2)) ? z : w;
 }
-// lane L of the lane's DPP row (exact: 0 + 1 * x; a -0 becomes +0).  Used only in straight-line
-// code without EXEC writes, so the DPP source hazard needs 2 wait states, not 5.
+// lane L of the lane's DPP row
 template <int L>
-__device__ __forceinline__ double rbcast(double x, double one) {
-#ifdef MPCQP_RBCAST_FMA
-  double acc = 0.0;
-  asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
-      : "+&v"(acc)
-      : "v"(x), "v"(one), "i"(L));
-  return acc;
-#else
-  (void)one;  // one v_mov_b64_dpp; the compiler sees it and inserts the DPP wait states itself
+__device__ __forceinline__ double rbcast(double x) {
+  // one v_mov_b64_dpp; the compiler sees it and inserts the DPP wait states itself
   return __builtin_amdgcn_update_dpp(0.0, x, 0x150 + L, 0xF, 0xF, false);
-#endif
 }
 // 1 / d: hardware reciprocal + two Newton steps (correct to the last bit or one ulp; the pivots of
 // an SPD matrix are positive and normal)
@@ -657,18 +515,17 @@ __device__ __forceinline__ double recip(double d) {
 // pivots, no pivoting: stable for SPD).  Pad rows / columns 12-15 must hold the identity.
 __device__ __forceinline__ void gj_inverse12(mf4& g) {
   const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
-  const double one = 1.0;
   sfor<0, 12>([&](auto P) __attribute__((always_inline)) {
     constexpr int p = decltype(P)::value, vp = p / 4, gp = p % 4;
     const double rowp = bcast_group<gp>(g[vp]);  // G[p][j]
-    const double piv = rbcast<p>(rowp, one);     // G[p][p]
+    const double piv = rbcast<p>(rowp);     // G[p][p]
     const double pinv = recip(piv);
     const double rs = rowp * pinv;
     const bool jp = j == p;
     // register 3 holds the pad rows 12-15: identity, zero in every pivot column, never changes
 #pragma unroll
     for (int v = 0; v < 3; ++v) {
-      const double col = rbcast<p>(g[v], one);  // G[4v + grp][p]
+      const double col = rbcast<p>(g[v]);  // G[4v + grp][p]
       const double upd = jp ? -col * pinv : g[v] - col * rs;
       if (v == vp) g[v] = (grp == gp) ? (jp ? pinv : rs) : upd;  // row p
       else g[v] = upd;
@@ -759,14 +616,7 @@ __device__ void factorize_mfma(SM& sm, const mpcqp_params& p, const Adisc& A, do
   wave_sync();
 }
 
-// ---- OSQP scale_data (scaling.c) as a kernel of its own -------------------------------------------
-// Ruiz equilibration is embarrassingly parallel over the columns of P~ = c D H D, so it runs before
-// wave_kernel with one thread per column (NTS threads per robot) and, for n <= 128, the column of H
-// generated once into registers instead of once per pass.  It writes a per-robot image (ScaleImg:
-// D, E, the scaled gradient q~, c, the warm-start branch, and for warm slots the raw gradient) that
-// wave_kernel reads in place of its own setup.  H's columns come from the same closed
-// form as before (see gen_col), so every norm is binary64; only the order of the cost-scaling sum
-// over columns differs from the single-wave version (a different but equally exact summation).
+// ---- what scale_kernel (mpcqp_scale.hip) and wave_kernel share: thresholds, the image, H's columns --
 // B6_k Gram pivot ratio below which a robot is handed to the Riccati form (scale_kernel's screen)
 #ifndef MPCQP_SCHUR_GRAM_TOL
 #define MPCQP_SCHUR_GRAM_TOL 1e-6
@@ -801,75 +651,6 @@ struct ScaleImg {
                        SIZE = DEGEN + 1;
   static_assert(SIZE == scale_image_doubles(N), "scale image layout");
 };
-
-template <int N>
-struct ScaleCfg {
-  static constexpr int n = ND * N, m = CD * N;
-  // Columns of H cached in registers across the passes (off: since the bound-decided passes, H is
-  // generated once per robot, and without the cache four robots fit a CU at N = 10)
-#ifndef MPCQP_SCALE_HREG_MAXN
-#define MPCQP_SCALE_HREG_MAXN 0
-#endif
-  static constexpr bool HREG = N <= MPCQP_SCALE_HREG_MAXN;
-#ifndef MPCQP_SCALE_TPC
-#define MPCQP_SCALE_TPC 2
-#endif
-#ifndef MPCQP_SCALE_TPC_LONG
-#define MPCQP_SCALE_TPC_LONG 1
-#endif
-  static constexpr int TPC = HREG ? MPCQP_SCALE_TPC : MPCQP_SCALE_TPC_LONG;  // threads per column (adjacent lanes)
-  static constexpr int BPT = (N + TPC - 1) / TPC;    // horizon blocks of the column per thread
-  // at least two waves: wave 1 runs the degenerate-feet screen (one lane per horizon step) while
-  // wave 0 runs the gradient sweep, so N <= 5 (n <= 60) still launches threads 64 .. 64 + N - 1
-  static constexpr int NTS = ((TPC * n + 63) / 64) * 64 > 64 + N ? ((TPC * n + 63) / 64) * 64 : ((64 + N + 63) / 64) * 64;
-  static constexpr int NWS = NTS / 64;
-  // waves per SIMD the register allocation must allow (launch bounds): two, i.e. 256 VGPRs and no
-  // spills.  N = 10: two waves per robot, four robots per CU; N = 20: four waves per robot, two per
-  // CU (three per CU spilled 43 VGPRs: the same step time, 21 MB more HBM traffic per C4 solve,
-  // profiles/r05/w20; three waves at N = 10 is slower, profiles/r05/sweep_reg)
-#ifdef MPCQP_SCALE_WPE
-  static constexpr int WPE = MPCQP_SCALE_WPE;
-#else
-  static constexpr int WPE = 2;
-#endif
-  static constexpr int RPT = (m + NTS - 1) / NTS;   // constraint rows per thread
-};
-
-template <int N>
-struct ScaleSmem {
-  using C = Cfg<N>;
-  alignas(16) double Bw[N][3][ND];
-  double rec[C::REC];
-  double D[2][C::n], q[C::n], qn[C::n], E[2][C::m];  // D, E double-buffered over the Ruiz passes
-  double lam[N][ND];
-  double vec[2][16];
-  double Ap[2][C::m];
-  double red[2][16];
-  double cm0[C::n];      // raw column norms of H (the first pass, D = 1)
-  double red4[2][5 * 16];  // bound passes: per-wave partials, double-buffered by pass parity
-};
-
-// block-wide sum of sv and max of qv in one barrier (wave partials summed in wave order)
-template <int NW>
-__device__ __forceinline__ void block_sum_max(double& sv, double& qv, double (*red)[16]) {
-  sv = wave_sum(sv);
-  qv = wave_max(qv);
-  if constexpr (NW > 1) {
-    if ((threadIdx.x & 63) == 0) {
-      red[0][threadIdx.x >> 6] = sv;
-      red[1][threadIdx.x >> 6] = qv;
-    }
-    __syncthreads();
-    double s = red[0][0], q = red[1][0];
-#pragma unroll
-    for (int i = 1; i < NW; ++i) {
-      s += red[0][i];
-      q = fmax(q, red[1][i]);
-    }
-    sv = s;
-    qv = q;
-  }
-}
 
 // Column c of H = B'Q̄B + R in closed form (A_c is nilpotent on the 12 moving states, A_c^2 = 0,
 // so A^m = I + m Ac with Ac := dt A_c, and

@@ -1,6 +1,6 @@
 """Foot geometries that make B6_k rank deficient or nearly so, and the host restatement of
-scale_kernel's Gram screen (csrc/mpcqp_wave.hip, "Degenerate-foot screen").  Pure numpy: the GPU
-tests (test_gpu_degenerate.py), the CPU tests and tools/r06_degen_sweep.py share it.
+scale_kernel's Gram screen (csrc/mpcqp_scale.hip, "Degenerate-foot screen").  Pure numpy: the GPU
+tests (test_gpu_degenerate.py) and the CPU tests share it.
 
 B6_k (rows 6-11 of B_d(k), ConvexMpc.cpp:132-143, Utils.cpp:35-41): rows 0-2 = I_w^-1 [r_l]x dt per
 leg l, rows 3-5 = dt/m I per leg.  The screen takes the Cholesky pivots of the Gram matrix

@@ -3,8 +3,8 @@
 
 The solve kernels issue hand-written DPP / permlane / LDS instructions from inline asm, which the
 compiler's hazard recognizer and waitcnt pass do not see into.  This tool reads the assembly of
-csrc/mpcqp_wave.hip (the inline asm is printed verbatim between ;;#ASMSTART / ;;#ASMEND) and checks,
-in program order, the hazards that can corrupt a value silently:
+csrc/mpcqp_wave.hip and csrc/mpcqp_scale.hip (the inline asm is printed verbatim between ;;#ASMSTART /
+;;#ASMEND) and checks, in program order, the hazards that can corrupt a value silently:
 
   dpp        a DPP instruction whose DPP source (src0) was written by a VALU instruction fewer than
              2 wait states before (CDNA3/4 ISA, "manually inserted wait states": VALU write VGPR ->
@@ -22,7 +22,7 @@ in program order, the hazards that can corrupt a value silently:
 Wait states: every instruction issued counts 1, `s_nop N` counts N + 1.  The scan is linear inside
 each kernel; a label resets nothing (conservative for fall-through, approximate across branches).
 
-  python tools/isa_hazards.py [--asm /tmp/wave.s] [--n 10] [--kernels wave_kernelILi10ELi1E ...]
+  python tools/isa_hazards.py [--asm /tmp/wave.s /tmp/scale.s] [--n 10] [--kernels wave_kernelILi10ELi1E ...]
 Exit status 1 if any hazard is found (the build's static check).
 """
 import argparse
@@ -33,7 +33,8 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(REPO, "go1-qp-mpc-controller_amd", "csrc", "mpcqp_wave.hip")
+CSRC = os.path.join(REPO, "go1-qp-mpc-controller_amd", "csrc")
+SRCS = [os.path.join(CSRC, "mpcqp_wave.hip"), os.path.join(CSRC, "mpcqp_scale.hip")]  # wave_kernel, scale_kernel
 
 REG = re.compile(r"\b([vas])(\d+)\b|\b([vas])\[(\d+):(\d+)\]")
 DPP_CTRL = ("row_newbcast", "quad_perm", "row_shl", "row_shr", "row_ror", "row_bcast", "row_share",
@@ -133,10 +134,14 @@ class Ins:
         return self.op.startswith("ds_")
 
 
-def kernels(asm_text, names):
+def kernels(asm_texts, names):
+    """(name, body lines, first line number) of each kernel, from whichever assembly file holds it"""
     for nm in names:
-        m = re.search(r"^(_ZN5mpcqp2wv\d+%s\S*):" % re.escape(nm), asm_text, re.M)
-        if not m:
+        for asm_text in asm_texts:
+            m = re.search(r"^(_ZN5mpcqp2wv\d+%s\S*):" % re.escape(nm), asm_text, re.M)
+            if m:
+                break
+        else:
             raise SystemExit(f"kernel {nm} not found")
         end = asm_text.index(".Lfunc_end", m.end())
         yield nm, asm_text[m.end():end].splitlines(), asm_text[:m.end()].count("\n") + 1
@@ -215,7 +220,8 @@ def check(lines, first_line):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--asm", default=None, help="assembly file (default: compile csrc/mpcqp_wave.hip)")
+    ap.add_argument("--asm", nargs="+", default=None,
+                    help="assembly files (default: compile csrc/mpcqp_wave.hip and csrc/mpcqp_scale.hip)")
     ap.add_argument("--n", type=int, default=10)
     ap.add_argument("--all", action="store_true",
                     help="the product build's every horizon (N = 1..20: wave_kernel<N, 1> for N <= 10, "
@@ -224,16 +230,20 @@ def main():
     ap.add_argument("--kernels", nargs="*", default=None)
     ap.add_argument("--max-report", type=int, default=40)
     a = ap.parse_args()
-    path = a.asm
-    if path is None:
-        path = os.path.join(tempfile.mkdtemp(), "w.s")
+    paths = a.asm
+    if paths is None:
+        tmp = tempfile.mkdtemp()
+        paths = [os.path.join(tmp, os.path.basename(src).replace(".hip", ".s")) for src in SRCS]
         nflag = [] if a.all else [f"-DMPCQP_WAVE_FOR_EACH_N(X)=X({a.n})"]
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-strict-aliasing",
-                        "-mllvm", "-amdgpu-mfma-vgpr-form"]
-                       + nflag + ["--cuda-device-only", "-S", SRC, "-o", path] + a.defs
-                       + os.environ.get("ISA_EXTRA_FLAGS", "").split(),
-                       check=True, stderr=subprocess.DEVNULL)
-    text = open(path).read()
+        cmds = [["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-strict-aliasing",
+                 "-mllvm", "-amdgpu-mfma-vgpr-form"]
+                + nflag + ["--cuda-device-only", "-S", src, "-o", path] + a.defs
+                + os.environ.get("ISA_EXTRA_FLAGS", "").split() for src, path in zip(SRCS, paths)]
+        procs = [subprocess.Popen(cmd, stderr=subprocess.DEVNULL) for cmd in cmds]  # side by side
+        for cmd, pr in zip(cmds, procs):
+            if pr.wait() != 0:
+                raise subprocess.CalledProcessError(pr.returncode, cmd)
+    texts = [open(path).read() for path in paths]
     if a.kernels:
         names = a.kernels
     elif a.all:
@@ -243,7 +253,7 @@ def main():
         names = ([f"wave_kernelILi{a.n}ELi1E"] if a.n <= 10 else []) + [f"wave_kernelILi{a.n}ELi0E", f"scale_kernelILi{a.n}E"]
     total = 0
     seen = 0
-    for nm, lines, l0 in kernels(text, names):
+    for nm, lines, l0 in kernels(texts, names):
         seen += 1
         probs, nins = check(lines, l0)
         kinds = {}

@@ -1,6 +1,7 @@
 """Static ISA accounting of wave_kernel<N, KS> per phase: compiles csrc/mpcqp_wave.hip for one
 horizon with -DMPCQP_ISA_MARKS (WV_MARK ids become assembly comments) and counts, between
 consecutive marks in program order, VALU / fp64 FMA / DPP / accvgpr moves / LDS / scratch ops.
+scale_kernel (csrc/mpcqp_scale.hip, compiled beside it) has no marks: one row with its totals.
 
   python tools/isa_phases.py [--n 10] [--ks 1] [--defs -DFOO] [--keep /tmp/w.s]
 """
@@ -12,6 +13,7 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "go1-qp-mpc-controller_amd", "csrc", "mpcqp_wave.hip")
+SCALE_SRC = os.path.join(REPO, "go1-qp-mpc-controller_amd", "csrc", "mpcqp_scale.hip")
 
 
 def compile_asm(n, defs, out, src=SRC):
@@ -52,6 +54,7 @@ def main():
     ap.add_argument("--defs", nargs="*", default=[])
     ap.add_argument("--keep", default=None)
     ap.add_argument("--src", default=SRC)
+    ap.add_argument("--scale-src", default=SCALE_SRC)
     a = ap.parse_args()
     out = a.keep or os.path.join(tempfile.mkdtemp(), "w.s")
     compile_asm(a.n, a.defs, out, a.src)
@@ -78,6 +81,19 @@ def main():
     for seg, c in rows:
         print("%-10s" % seg + "".join("%8d" % c[k] for k in keys))
     print("%-10s" % "total" + "".join("%8d" % tot[k] for k in keys))
+    # scale_kernel<N>, the launch before wave_kernel
+    sout = os.path.join(os.path.dirname(out), "scale.s")
+    compile_asm(a.n, a.defs, sout, a.scale_src)
+    s = open(sout).read()
+    m = re.search(r"^(_ZN5mpcqp2wv12scale_kernelILi%dEE\S*):" % a.n, s, re.M)
+    sc = {k: 0 for k in keys}
+    for line in s[m.end(): s.index(".Lfunc_end", m.end())].splitlines():
+        t = line.strip()
+        if not t or t.startswith((";", ".", "//")) or t.endswith(":"):
+            continue
+        for k, v in classify(t).items():
+            sc[k] += v
+    print("%-10s" % "scale" + "".join("%8d" % sc[k] for k in keys))
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""scale_kernel phase timing: run a library built with -DMPCQP_SCALE_TIMING (tools/build_variant.sh
-OUT.so 10 -DMPCQP_SCALE_TIMING, selected with MPCQP_LIB; MPCQP_N=20 for another horizon); thread 0 of each robot writes {id,
+"""scale_kernel phase timing: run a library built with -DMPCQP_SCALE_TIMING (`make -C
+go1-qp-mpc-controller_amd variant OUT=../abtest/sct.so DEFS=-DMPCQP_SCALE_TIMING`, selected with
+MPCQP_LIB; MPCQP_N=20 for another horizon); thread 0 of each robot writes {id,
 s_memtime} pairs over its own record.  Reports median shader-clock cycles per phase: 0 -> 1 record
 load + B_w + gradient sweeps, 1 -> 2 column init, 2 -> 3 first column pass (H columns generated),
 3 -> 4 Ruiz pass 0, 4 -> 5 passes 1..9, 5 -> 6 image write; and the robot's whole span; 7 = kernel
