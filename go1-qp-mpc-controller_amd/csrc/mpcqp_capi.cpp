@@ -37,6 +37,18 @@ struct mpcqp_handle {
   hipStream_t sub[KMAX] = {};
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_join[KMAX] = {};
+  // Launch-order hint of the wave path (mpcqp_order.hip; mpcqp_internal.h OrderHint): per robot the
+  // cost key and contact mask of its last solve and this solve's order, per part the layout the state
+  // was written for.  Sized and zero-filled with the workspace; validity is decided on the device.
+  int order_hint = -1;       // -1 per-path default (order_hint_default), 0 off, 1 on: MPCQP_ORDER_HINT / mpcqp_set_order_hint
+  int* ord_order = nullptr;
+  int* ord_key = nullptr;
+  int* ord_contacts = nullptr;
+  int* ord_layout = nullptr;  // [KMAX][ORDER_LAYOUT_INTS]
+  // the last wave-path solve, for mpcqp_debug_launch_order
+  int last_batch = 0, last_parts = 0;
+  bool last_hint = false;
+  int last_bnd[KMAX + 1] = {};
   int path = 0;              // 0 auto (= 3), 3 Riccati wave; debug library only: 1 dense K^-1, 2 Riccati workgroup
   // host wrapper: device buffers, a private stream and two pinned staging chunks
   hipStream_t hstream = nullptr;
@@ -119,14 +131,25 @@ hipError_t ensure_workspace(mpcqp_handle* h, int32_t batch, void* stream) {
   hipError_t e = hipStreamSynchronize((hipStream_t)stream);
   if (e == hipSuccess) e = hipFree(h->work);
   if (e == hipSuccess) e = hipFree(h->fb);
+  if (e == hipSuccess) e = hipFree(h->ord_order);  // (one allocation: order, key, contacts, layout)
   h->work = nullptr;
   h->fb = nullptr;
+  h->ord_order = h->ord_key = h->ord_contacts = h->ord_layout = nullptr;
   const size_t cap = (size_t)batch > h->work_cap ? (size_t)batch : h->work_cap;
   h->work_cap = 0;
   h->work_per = 0;
   if (e == hipSuccess) e = hipMalloc(&h->work, sizeof(double) * per * cap);
   if (e == hipSuccess) e = hipMalloc(&h->fb, sizeof(int) * 4 * mpcqp_handle::KMAX);
   if (e == hipSuccess) e = hipMemset(h->fb, 0, sizeof(int) * 4 * mpcqp_handle::KMAX);
+  // the launch-order state starts zero-filled: no part's layout matches a batch of zero robots
+  const size_t ord_ints = 3 * cap + (size_t)mpcqp::ORDER_LAYOUT_INTS * mpcqp_handle::KMAX;
+  if (e == hipSuccess) e = hipMalloc(&h->ord_order, sizeof(int) * ord_ints);
+  if (e == hipSuccess) e = hipMemset(h->ord_order, 0, sizeof(int) * ord_ints);
+  if (e == hipSuccess) {
+    h->ord_key = h->ord_order + cap;
+    h->ord_contacts = h->ord_key + cap;
+    h->ord_layout = h->ord_contacts + cap;
+  }
   if (e == hipSuccess) {
     h->work_cap = cap;
     h->work_per = per;
@@ -144,6 +167,19 @@ int split_parts(const mpcqp_handle* h, int32_t batch) {
   if (k > mpcqp_handle::KMAX) k = mpcqp_handle::KMAX;
   if (k > batch) k = batch;
   return k < 1 ? 1 : k;
+}
+
+// Whether a wave-path solve (cold, or warm-started from slots) takes its launch order from the
+// handle's hint state.  The built-in defaults are per path and set by measurement on records that
+// change every call (tools/order_hint_ab.py, profiles/order_hint; DESIGN 5 "Launch order"): 4096
+// robots over 40 consecutive ticks, median ms per tick, cold 1.327 -> 1.259 and 1.342 -> 1.250,
+// warm 0.691 -> 0.647 and 0.654 -> 0.618 (swing_ticks 5 and 40), each gain several times the
+// hint-off repetitions' spread.  A path whose gain falls inside that spread goes back to false.
+constexpr bool ORDER_HINT_DEFAULT_COLD = true;
+constexpr bool ORDER_HINT_DEFAULT_WARM = true;
+bool order_hint_on(const mpcqp_handle* h, bool warm) {
+  if (h->order_hint >= 0) return h->order_hint != 0;
+  return warm ? ORDER_HINT_DEFAULT_WARM : ORDER_HINT_DEFAULT_COLD;
 }
 
 // The internal streams and events of a split into `parts` parts: parts 1 .. parts-1 each get a stream
@@ -287,6 +323,10 @@ int32_t mpcqp_create(const mpcqp_params* params, int32_t device, mpcqp_handle** 
   h->slots = cus * per_cu;
   h->cus = cus;
   if (const char* sp = getenv("MPCQP_SPLIT")) h->split = atoi(sp);
+  if (const char* oh = getenv("MPCQP_ORDER_HINT")) {
+    const int v = atoi(oh);
+    h->order_hint = v < 0 ? -1 : v != 0;
+  }
   if (const char* sw = getenv("MPCQP_SPLIT_W")) {
     for (int i = 0; i < mpcqp_handle::KMAX && *sw; ++i) {
       char* end = nullptr;
@@ -305,6 +345,7 @@ int32_t mpcqp_destroy(mpcqp_handle* h) {
   DeviceGuard dg(h->device);
   (void)hipFree(h->work);
   (void)hipFree(h->fb);
+  (void)hipFree(h->ord_order);
   (void)hipFree(h->d_recs);
   (void)hipFree(h->d_res);
   (void)hipFree(h->d_sol);
@@ -351,6 +392,7 @@ static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32
   a.grid = batch;
   a.stream = stream;
   a.p = h->p;
+  a.hint = mpcqp::OrderHint{};  // input order (the cross-check paths ignore the hint)
   switch (effective_path(h)) {
 #ifdef MPCQP_DEBUG_PATHS
     case 1: e = mpcqp::launch_solve_any(a); break;
@@ -359,8 +401,28 @@ static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32
     default: {
       const int parts = split_parts(h, batch);
       h->fb_parts = parts;
+      const bool hint = order_hint_on(h, d_state != nullptr);
+      h->last_batch = batch;
+      h->last_parts = parts;
+      h->last_hint = hint;
+      // part i's order_kernel, ahead of its scale_kernel and wave_kernel on the part's stream
+      auto order_part = [&](mpcqp::LaunchArgs& ai, int i, int b0) {
+        if (!hint) return hipSuccess;
+        ai.hint.order = h->ord_order + b0;
+        ai.hint.key = h->ord_key + b0;
+        ai.hint.contacts = h->ord_contacts + b0;
+        ai.hint.layout = h->ord_layout + mpcqp::ORDER_LAYOUT_INTS * i;
+        ai.hint.whole = batch;
+        ai.hint.parts = parts;
+        ai.hint.part = i;
+        ai.hint.first = b0;
+        return mpcqp::launch_order(ai, mpcqp_handle::KMAX);
+      };
       if (parts == 1) {
-        e = mpcqp::launch_wave_any(a);
+        h->last_bnd[0] = 0;
+        h->last_bnd[1] = batch;
+        e = order_part(a, 0, 0);
+        if (e == hipSuccess) e = mpcqp::launch_wave_any(a);
         break;
       }
       // fork: part 0 runs on the caller's stream, every other part on an internal stream that waits
@@ -381,6 +443,7 @@ static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32
       }
       for (int i = 0; i < parts && weighted; ++i) weighted = bnd[i + 1] > bnd[i];
       for (int i = 0; i <= parts && !weighted; ++i) bnd[i] = (int)((int64_t)batch * i / parts);
+      for (int i = 0; i <= parts; ++i) h->last_bnd[i] = bnd[i];
       for (int i = 0; i < parts && e == hipSuccess; ++i) {
         const int b0 = bnd[i], b1 = bnd[i + 1];
         mpcqp::LaunchArgs ai = a;
@@ -396,11 +459,13 @@ static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32
         ai.fallback = h->fb + 4 * i;
         if (i == 0) {
           ai.stream = stream;
-          e = mpcqp::launch_wave_any(ai);
+          e = order_part(ai, i, b0);
+          if (e == hipSuccess) e = mpcqp::launch_wave_any(ai);
           continue;
         }
         ai.stream = h->sub[i];
         e = hipStreamWaitEvent(h->sub[i], h->ev_fork, 0);
+        if (e == hipSuccess) e = order_part(ai, i, b0);
         if (e == hipSuccess) e = mpcqp::launch_wave_any(ai);
         if (e == hipSuccess) e = hipEventRecord(h->ev_join[i], h->sub[i]);
       }
@@ -723,6 +788,29 @@ int32_t mpcqp_debug_set_split(mpcqp_handle* h, int32_t parts) {
   const int32_t old = h->split;
   h->split = parts;
   return old;
+}
+
+int32_t mpcqp_set_order_hint(mpcqp_handle* h, int32_t on) {
+  if (!h || on < -1 || on > 1) return -2;
+  const int32_t old = h->order_hint;
+  h->order_hint = on;
+  return old;
+}
+
+int32_t mpcqp_debug_launch_order(mpcqp_handle* h, int32_t* host_out, int32_t cap) {
+  if (!h || cap < 0 || (cap > 0 && !host_out)) return -MPCQP_ERR_INVALID_ARG;
+  const int32_t nout = h->last_batch < cap ? h->last_batch : cap;
+  for (int32_t i = 0; i < nout; ++i) host_out[i] = i;
+  if (!h->last_hint || !h->ord_order || nout == 0) return nout;
+  DeviceGuard g(h->device);
+  hipError_t e = g.err;
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(host_out, h->ord_order, sizeof(int32_t) * nout, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return -set_hip_error(h, e, "mpcqp_debug_launch_order");
+  // a part's order holds part-local indices
+  for (int i = 0; i < h->last_parts; ++i)
+    for (int b = h->last_bnd[i]; b < h->last_bnd[i + 1] && b < nout; ++b) host_out[b] += h->last_bnd[i];
+  return nout;
 }
 
 int32_t mpcqp_debug_split_parts(mpcqp_handle* h, int32_t batch) {

@@ -9,6 +9,35 @@
 namespace mpcqp {
 
 
+// Launch-order hint of the wave path (mpcqp_order.hip), handle-owned device state.  The arrays are
+// indexed by global batch index; a part of a split solve gets them offset to its first robot, and
+// its order[] holds part-local indices.  order == nullptr: robots are dispatched in input order and
+// nothing of the state is read or written.
+constexpr int ORDER_KEY_MAX = 63;     // cost keys are clamped to 0 .. ORDER_KEY_MAX
+constexpr int ORDER_KEY_SHIFT = 3;    // key = cost >> ORDER_KEY_SHIFT
+constexpr int ORDER_RHO_WEIGHT = 15;  // one rho update (refactorization) costs about 15 iterations
+constexpr int ORDER_COST_MAX = 1 << 20;
+constexpr int ORDER_LAYOUT_INTS = 4;  // per part: {whole batch, parts, first robot, robots}
+// what a solve cost, in iterations (a robot handed from the Schur to the Riccati form: both added)
+__host__ __device__ constexpr int order_cost(int iters, int rho_updates) {
+  const int it = iters < 0 ? 0 : iters > ORDER_COST_MAX ? ORDER_COST_MAX : iters;
+  const int ru = rho_updates < 0 ? 0 : rho_updates > ORDER_COST_MAX ? ORDER_COST_MAX : rho_updates;
+  return it + ORDER_RHO_WEIGHT * ru;  // < 2^25
+}
+__host__ __device__ constexpr int order_key(int cost) {
+  const int k = cost >> ORDER_KEY_SHIFT;
+  return k < 0 ? 0 : k > ORDER_KEY_MAX ? ORDER_KEY_MAX : k;
+}
+struct OrderHint {
+  int* order;     // [robots] written by order_kernel, read by wave_kernel: block i solves robot order[i]
+  int* key;       // [robots] cost key of the robot's last solve, written by wave_kernel's epilogue
+  int* contacts;  // [robots] contact mask (bit l = leg l) the robot was last solved with (order_kernel)
+  int* layout;    // this part's ORDER_LAYOUT_INTS: the batch and part layout the state was written for
+  int whole, parts, part, first;  // this call's layout: whole batch, parts, this part, its first robot
+};
+
+// One (part of a) solve.  recs .. wstate and hint.order/key/contacts point at the part's first robot
+// and batch / grid count the part's robots; fallback and hint.layout are the part's own.
 struct LaunchArgs {
   const double* recs;
   int batch;
@@ -23,6 +52,7 @@ struct LaunchArgs {
   int grid;
   void* stream;
   mpcqp_params p;
+  OrderHint hint;  // wave path: launch order (hint.order == nullptr: input order)
 };
 
 // Formulation only (mpcqp_build.hip): ConvexMpc::calculate_qp_mats, horizons 1..20
@@ -34,6 +64,9 @@ hipError_t launch_wave_any(const LaunchArgs& a);
 hipError_t occupancy_wave_any(const mpcqp_params& p, int* blocks);
 hipError_t wave_selftest(double* d_out, void* stream);
 hipError_t launch_scale_any(const LaunchArgs& a);  // scale_kernel alone (the image in a.work)
+// order_kernel (mpcqp_order.hip): a.hint.order for this part from the stored keys and contact masks,
+// the identity when the state was written for another layout; kmax = layout slots the handle owns
+hipError_t launch_order(const LaunchArgs& a, int kmax);
 constexpr int WAVE_MAX_HORIZON = 20;
 // the horizons both files instantiate their kernels for (static ISA tools build a single one)
 #ifndef MPCQP_WAVE_FOR_EACH_N

@@ -86,14 +86,17 @@ namespace wv {
 
 // KS: the KKT solve.  0 = Riccati recursion (chains over the horizon, factors on MFMA; every N),
 // 1 = impulse-space Schur form (mpcqp_schur.h; N <= 10, nonnegative state weights).
-// The solve of robot `inst` by one wave (wave_kernel: one robot per workgroup).  Returns true when a
-// KS = 1 solve hands the robot to the Riccati form without having written anything: scale_kernel
+// The solve of robot `inst` by one wave (wave_kernel: one robot per workgroup).  Returns what the
+// solve cost (order_cost of its iterations and rho updates, for the launch-order hint's key), with
+// WAVE_HANDOFF set when a KS = 1 solve
+// hands the robot to the Riccati form without having written anything: scale_kernel
 // flagged it (rank-deficient B6_k), a KKT solve cancelled too much for its core (S_max * amp >
 // SCHUR_AMP), or a factorization's max S_ii crossed SCHUR_SMAX; wave_kernel then solves it with
 // KS = 0 in the same wave.  fb counts the cases: [0] rank-deficient feet, [1] S_max * amp > SCHUR_AMP,
 // [2] S_max > SCHUR_SMAX, [3] unused.
+constexpr int WAVE_HANDOFF = 1 << 30;
 template <int N, int KS>
-__device__ __forceinline__ bool wave_solve(const int inst, WSmem<N, KS>& sm, const double* __restrict__ recs,
+__device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, const double* __restrict__ recs,
                                            mpcqp_result* __restrict__ results, double* __restrict__ solution,
                                            double* __restrict__ trace, int trace_cap, double* __restrict__ wstate,
                                            double* __restrict__ img, const mpcqp_params& p,
@@ -131,7 +134,7 @@ __device__ __forceinline__ bool wave_solve(const int inst, WSmem<N, KS>& sm, con
       }
       if (solution)
         for (int e = t; e < n; e += NT) solution[(size_t)inst * n + e] = NAN;
-      return false;
+      return 0;
     }
   }
   wave_sync();
@@ -187,7 +190,7 @@ __device__ __forceinline__ bool wave_solve(const int inst, WSmem<N, KS>& sm, con
     // still strictly convex, R > 0): the Riccati form (KS = 0) solves this robot.  Nothing of it
     // has been written yet.
     if (t == 0) atomicAdd(fb, 1);
-    return true;
+    return WAVE_HANDOFF;
   }
   for (int j = t; j < n; j += NT) {
     HS.D[j] = im[SI::D + j];
@@ -1159,7 +1162,7 @@ __device__ __forceinline__ bool wave_solve(const int inst, WSmem<N, KS>& sm, con
   WV_MARK(20);
   if (KS == 1 && (amp_bad || !(img_at(SI::DEGEN) <= SCHUR_SMAX))) {  // the Riccati form solves it
     if (t == 0) atomicAdd(fb + (amp_bad ? 1 : 2), 1);
-    return true;
+    return WAVE_HANDOFF | order_cost(iters, rho_updates);
   }
   if (ws) {  // the solver persists: scaling, scaled data, iterates and rho for the next tick
     if (t == 0) {
@@ -1243,7 +1246,7 @@ __device__ __forceinline__ bool wave_solve(const int inst, WSmem<N, KS>& sm, con
     res->iters = iters;
     res->rho_updates = rho_updates;
   }
-  return false;
+  return order_cost(iters, rho_updates);
 }
 
 // (one wave per SIMD: the whole register file; two robots per SIMD, a 256-register budget, was
@@ -1254,8 +1257,12 @@ __global__ __launch_bounds__(NT, 1) void wave_kernel(const double* __restrict__ 
                                                      double* __restrict__ solution, double* __restrict__ trace,
                                                      int trace_cap, double* __restrict__ wstate,
                                                      double* __restrict__ img, mpcqp_params p,
-                                                     int* __restrict__ fb) {
-  const int inst = blockIdx.x;
+                                                     int* __restrict__ fb, const int* __restrict__ order,
+                                                     int* __restrict__ key) {
+  // launch order (mpcqp_order.hip): block i solves robot order[i]; everything below follows inst.
+  // An index outside the batch solves nothing.
+  const int inst = order ? order[blockIdx.x] : (int)blockIdx.x;
+  int cost;
   if constexpr (KS == 1) {
     // The Schur form, and in the same wave the Riccati form for the robots it hands over (the two
     // forms' LDS images share one allocation: the Riccati factors fit inside the Schur core's)
@@ -1263,16 +1270,20 @@ __global__ __launch_bounds__(NT, 1) void wave_kernel(const double* __restrict__ 
       WSmem<N, 1> s;
       WSmem<N, 0> r;
     } sm;
-    if (inst >= batch) return;
-    if (wave_solve<N, 1>(inst, sm.s, recs, results, solution, trace, trace_cap, wstate, img, p, fb)) {
+    if ((unsigned)inst >= (unsigned)batch) return;
+    cost = wave_solve<N, 1>(inst, sm.s, recs, results, solution, trace, trace_cap, wstate, img, p, fb);
+    if (cost & WAVE_HANDOFF) {
       wave_sync();
-      wave_solve<N, 0>(inst, sm.r, recs, results, solution, trace, trace_cap, wstate, img, p, nullptr);
+      cost = (cost & ~WAVE_HANDOFF) +
+             wave_solve<N, 0>(inst, sm.r, recs, results, solution, trace, trace_cap, wstate, img, p, nullptr);
     }
   } else {
     __shared__ WSmem<N, 0> sm;
-    if (inst >= batch) return;
-    wave_solve<N, 0>(inst, sm, recs, results, solution, trace, trace_cap, wstate, img, p, fb);
+    if ((unsigned)inst >= (unsigned)batch) return;
+    cost = wave_solve<N, 0>(inst, sm, recs, results, solution, trace, trace_cap, wstate, img, p, fb);
   }
+  // what the robot cost, for the next call's launch order
+  if (key && threadIdx.x == 0) key[inst] = order_key(cost);
 }
 
 // Self-test of the cross-lane primitives (mv12 broadcast lanes, rmove directions): out[64*k + lane].
@@ -1303,15 +1314,18 @@ template <int N>
 static hipError_t launch_wave(const LaunchArgs& a) {
   const hipError_t e = launch_scale_any(a);  // scale_kernel first, on the same stream (mpcqp_scale.hip)
   if (e != hipSuccess) return e;
+  const int* ord = a.hint.order;  // written by order_kernel on the same stream, or nullptr: input order
+  int* key = ord ? a.hint.key : nullptr;
   if constexpr (N <= 10) {
     if (schur_ok(a.p)) {
       hipLaunchKernelGGL((wv::wave_kernel<N, 1>), dim3(a.batch), dim3(wv::NT), 0, (hipStream_t)a.stream, a.recs,
-                         a.batch, a.results, a.solution, a.trace, a.trace_cap, a.wstate, a.work, a.p, a.fallback);
+                         a.batch, a.results, a.solution, a.trace, a.trace_cap, a.wstate, a.work, a.p, a.fallback,
+                         ord, key);
       return hipGetLastError();
     }
   }
   hipLaunchKernelGGL((wv::wave_kernel<N, 0>), dim3(a.batch), dim3(wv::NT), 0, (hipStream_t)a.stream, a.recs, a.batch,
-                     a.results, a.solution, a.trace, a.trace_cap, a.wstate, a.work, a.p, a.fallback);
+                     a.results, a.solution, a.trace, a.trace_cap, a.wstate, a.work, a.p, a.fallback, ord, key);
   return hipGetLastError();
 }
 // occupancy of the wave kernel a handle with these parameters launches (the KS choice of launch_wave)

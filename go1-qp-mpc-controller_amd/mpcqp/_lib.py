@@ -143,6 +143,7 @@ EXPORTED = [
     "mpcqp_debug_scale_image_doubles", "mpcqp_debug_scale_image_device", "mpcqp_copy_warm_slots_device",
     "mpcqp_handoff_counts",
     "mpcqp_debug_set_split", "mpcqp_debug_split_parts",
+    "mpcqp_set_order_hint", "mpcqp_debug_launch_order",
     "mpcqp_plan_default_params", "mpcqp_plan_state_size", "mpcqp_leg_plan_device",
     "mpcqp_est_default_params", "mpcqp_est_params_size", "mpcqp_estimator_state_size",
     "mpcqp_state_estimate_device",
@@ -227,6 +228,11 @@ def load(debug=False):
     L.mpcqp_debug_set_split.restype = i32
     L.mpcqp_debug_split_parts.argtypes = [vp, i32]
     L.mpcqp_debug_split_parts.restype = i32
+    if hasattr(L, "mpcqp_set_order_hint"):  # (absent from an older library given by MPCQP_LIB for an A/B)
+        L.mpcqp_set_order_hint.argtypes = [vp, i32]
+        L.mpcqp_set_order_hint.restype = i32
+        L.mpcqp_debug_launch_order.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), i32]
+        L.mpcqp_debug_launch_order.restype = i32
     L.mpcqp_plan_default_params.argtypes = [ctypes.POINTER(PlanParams)]
     L.mpcqp_plan_default_params.restype = None
     L.mpcqp_plan_state_size.argtypes = []

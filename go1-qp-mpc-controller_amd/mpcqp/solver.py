@@ -69,6 +69,29 @@ class MpcQpSolver:
         """mpcqp_debug_split_parts: parts a solve of `batch` robots is split into."""
         return int(self._L.mpcqp_debug_split_parts(self._h, int(batch)))
 
+    def set_order_hint(self, on):
+        """mpcqp_set_order_hint: dispatch each solve's robots costliest-first from what they cost in
+        the handle's previous solve (1 on, 0 off, -1 the built-in default of cold and warm-started
+        solves).  Results do not depend on it.  Returns the previous setting."""
+        old = int(self._L.mpcqp_set_order_hint(self._h, int(on)))
+        if old < -1:
+            raise ValueError("mpcqp_set_order_hint: on must be -1, 0 or 1")
+        return old
+
+    def launch_order(self):
+        """mpcqp_debug_launch_order: the order in which the last wave-path solve dispatched its
+        robots, as global batch indices (int32 array; the identity without the hint).  Synchronizes
+        the device."""
+        cap = 1024
+        while True:
+            out = np.empty(cap, dtype=np.int32)
+            n = int(self._L.mpcqp_debug_launch_order(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cap))
+            if n < 0:
+                check(-n, self._h, "mpcqp_debug_launch_order", self._L)
+            if n < cap:
+                return out[:n].copy()
+            cap *= 8
+
     def handoff_counts(self):
         """mpcqp_handoff_counts: robots of the last Schur-form solve that the Riccati form solved in
         their own wave, as (rank-deficient feet, S_max x cancellation above SCHUR_AMP, S_max above the

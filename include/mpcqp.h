@@ -158,6 +158,20 @@ int32_t mpcqp_warm_state_size(int32_t horizon);
 int32_t mpcqp_solve_batch_warm_device(mpcqp_handle* h, const double* d_records, int32_t batch, double* d_state,
                                       mpcqp_result* d_results, double* d_solution, void* stream);
 
+/* Launch-order hint.  One wavefront solves one robot and robots differ several-fold in iterations,
+ * so the order in which a batch's robots are dispatched decides how long the last ones leave the
+ * device partly idle.  The handle remembers, per batch index, what the robot cost in the handle's
+ * previous solve and the contact set it was solved with; the next solve of the same batch size
+ * dispatches robots whose contact set changed first, then the costliest first.  Results do not
+ * depend on it by a bit.  The only contract is the warm slots' one: batch index b is the same robot
+ * as in the previous call on this handle; a caller that shuffles its robots loses the gain, nothing
+ * else.  The state lives on the device and is read when the solve runs, so replays of a solve
+ * captured into a hipGraph follow it too.
+ *   on: 1 both solves, 0 neither, -1 the built-in default of each (cold and warm-started solves
+ * have their own).  The environment variable MPCQP_ORDER_HINT sets the
+ * initial value at mpcqp_create.  Returns the previous setting, or -2 for a bad argument. */
+int32_t mpcqp_set_order_hint(mpcqp_handle* h, int32_t on);
+
 /* Indexed copy of warm-start slots between DEVICE buffers, for callers whose solved robots are a
  * subset of their slots (a mixed-mode batch: the MPC robots' slots gathered into a compact buffer
  * for the warm solve and scattered back after it, as the reference's controller keeps its member

@@ -42,6 +42,12 @@ int32_t mpcqp_debug_set_split(mpcqp_handle* h, int32_t parts);
 /* Parts a solve of `batch` robots on this handle is split into under its current setting. */
 int32_t mpcqp_debug_split_parts(mpcqp_handle* h, int32_t batch);
 
+/* The order in which the handle's last wave-path solve dispatched its robots (mpcqp_set_order_hint),
+ * as global batch indices: host_out[i] is the robot block i solved, the parts of a split solve one
+ * after another.  The identity for a solve that ran without the hint.  Writes min(batch, cap)
+ * entries to HOST memory and returns that count, or -MPCQP_ERR_* .  Synchronizes the device. */
+int32_t mpcqp_debug_launch_order(mpcqp_handle* h, int32_t* host_out, int32_t cap);
+
 /* Threads per robot workgroup of the solve kernel the default path uses for horizon N. */
 int32_t mpcqp_solve_threads(int32_t horizon);
 
