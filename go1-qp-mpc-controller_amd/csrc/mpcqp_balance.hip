@@ -15,18 +15,17 @@
 // (orc_balance_build_qp / ws_setup_dense / ws_admm) operation by operation with contraction off,
 // so the GPU reproduces the oracle's iterate sequence.  The QP is 12 x 20: per-robot work is
 // ~100 kFLOP (setup) + ~1.5 kFLOP per ADMM iteration, latency-bound, nowhere near HBM.
-#include "mpcqp_device.h"
-
+// Contraction off for the whole file, the included headers too: the rules of mpcqp_osqp.h (which
+// carries no pragma of its own) are compiled unfused here whatever the include order.
 #pragma clang fp contract(off)
+
+#include "mpcqp_device.h"
 
 namespace mpcqp {
 namespace bal {
 
 constexpr int n = MPCQP_NUM_DOF;         // 12
 constexpr int m = MPCQP_CONSTRAINT_DIM;  // 20
-constexpr double INF = MPCQP_OSQP_INFTY;
-constexpr double RHO_MIN_ = 1e-6, RHO_MAX_ = 1e6, RHO_EQ = 1e3, RHO_TOL_ = 1e-4;
-constexpr double DIV_TOL = 1.0 / MPCQP_OSQP_INFTY;
 
 // Structural nonzeros of the constraint matrix (ctor, A1RobotControl.cpp:27-44): row i < 4 is
 // F_zi (col 3i+2); row 4+4i+k has +-1 at col 3i+(k>>1) and -mu at col 3i+2.
@@ -49,7 +48,7 @@ struct Ws {
 };
 
 __device__ __forceinline__ double rho_of(const Ws& w, int r) {
-  return w.ctype[r] == -1 ? RHO_MIN_ : (w.ctype[r] == 1 ? RHO_EQ * w.rho : w.rho);
+  return osqp::rho_of_row(w.ctype[r], w.rho);
 }
 
 // K = P + sigma I + A' diag(rho) A, dense Cholesky (oracle factor_kkt, same accumulation order)
@@ -180,12 +179,7 @@ __device__ __forceinline__ void update_info(Ws& w, const mpcqp_params& p, int it
 __device__ __forceinline__ bool primal_infeasible(Ws& w, const mpcqp_params& p, double eps) {
   const bool sc = p.scaling && !p.scaled_termination;
 #pragma unroll
-  for (int r = 0; r < m; ++r) {
-    if (w.u[r] > INF * MIN_SCALING)
-      w.dy[r] = w.l[r] < -INF * MIN_SCALING ? 0.0 : dmin(w.dy[r], 0.0);
-    else if (w.l[r] < -INF * MIN_SCALING)
-      w.dy[r] = dmax(w.dy[r], 0.0);
-  }
+  for (int r = 0; r < m; ++r) w.dy[r] = osqp::polar_project(w.dy[r], w.l[r], w.u[r]);
   double nrm = 0.0;
 #pragma unroll
   for (int r = 0; r < m; ++r) {
@@ -235,8 +229,7 @@ __device__ __forceinline__ bool dual_infeasible(const Ws& w, const mpcqp_params&
 #pragma unroll
         for (int r = 0; r < m; ++r) {
           const double v = sc ? ad[r] * (1.0 / w.E[r]) : ad[r];
-          if (((w.u[r] < INF * MIN_SCALING) && (v > eps * nrm)) || ((w.l[r] > -INF * MIN_SCALING) && (v < -eps * nrm)))
-            ok = false;
+          if (osqp::dual_ray_violates(v, w.l[r], w.u[r], eps * nrm)) ok = false;
         }
         return ok;
       }
@@ -246,9 +239,9 @@ __device__ __forceinline__ bool dual_infeasible(const Ws& w, const mpcqp_params&
 }
 
 __device__ __forceinline__ int check_termination(Ws& w, const mpcqp_params& p, bool approximate) {
-  if ((w.pri_res > INF) || (w.dua_res > INF)) {
+  if ((w.pri_res > OSQP_INF) || (w.dua_res > OSQP_INF)) {
     w.status = MPCQP_STATUS_NON_CVX;
-    w.obj_val = __builtin_nan("");
+    w.obj_val = osqp::objective_of(w.status, 0.0, 0.0);
     return 1;
   }
   double eps_abs = p.eps_abs, eps_rel = p.eps_rel, eps_pinf = p.eps_prim_inf, eps_dinf = p.eps_dual_inf;
@@ -263,8 +256,7 @@ __device__ __forceinline__ int check_termination(Ws& w, const mpcqp_params& p, b
   {
     double mx = sc ? dmax(scaled_norm_inf<m>(w.E, w.z, true), scaled_norm_inf<m>(w.E, w.Ax, true))
                    : dmax(norm_inf<m>(w.z), norm_inf<m>(w.Ax));
-    const double eps_prim = eps_abs + eps_rel * mx;
-    if (w.pri_res < eps_prim)
+    if (w.pri_res < osqp::tolerance(eps_abs, eps_rel, mx))
       prim_ok = true;
     else
       prim_inf = primal_infeasible(w, p, eps_pinf);
@@ -279,52 +271,30 @@ __device__ __forceinline__ int check_termination(Ws& w, const mpcqp_params& p, b
     } else {
       mx = dmax(dmax(norm_inf<n>(w.q), norm_inf<n>(w.Aty)), norm_inf<n>(w.Px));
     }
-    const double eps_dual = eps_abs + eps_rel * mx;
-    if (w.dua_res < eps_dual)
+    if (w.dua_res < osqp::tolerance(eps_abs, eps_rel, mx))
       dual_ok = true;
     else
       dual_inf = dual_infeasible(w, p, eps_dinf);
   }
-  if (prim_ok && dual_ok) {
-    w.status = approximate ? MPCQP_STATUS_SOLVED_INACCURATE : MPCQP_STATUS_SOLVED;
-    return 1;
-  }
-  if (prim_inf) {
-    w.status = approximate ? MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_PRIMAL_INFEASIBLE;
-    w.obj_val = INF;
-    return 1;
-  }
-  if (dual_inf) {
-    w.status = approximate ? MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_DUAL_INFEASIBLE;
-    w.obj_val = -INF;
-    return 1;
-  }
-  return 0;
+  const int st = osqp::termination_status(prim_ok, dual_ok, prim_inf, dual_inf, approximate);
+  if (st == MPCQP_STATUS_UNSOLVED) return 0;
+  w.status = st;
+  if (!osqp::has_solution(st)) w.obj_val = osqp::objective_of(st, 0.0, 0.0);  // +-OSQP_INFTY of a certificate
+  return 1;
 }
 
 // compute_rho_estimate + adapt_rho (refactors on a change); returns the factorisation failure flag
 __device__ __forceinline__ int adapt_rho(Ws& w, const mpcqp_params& p) {
-  double pri = norm_inf<m>(w.zp);
-  double dua = norm_inf<n>(w.xp);
   const double pn = dmax(norm_inf<m>(w.z), norm_inf<m>(w.Ax));
-  pri /= (pn + DIV_TOL);
   const double dn = dmax(dmax(norm_inf<n>(w.q), norm_inf<n>(w.Aty)), norm_inf<n>(w.Px));
-  dua /= (dn + DIV_TOL);
-  double est = w.rho * __builtin_sqrt(pri / (dua + DIV_TOL));
-  est = dmin(dmax(est, RHO_MIN_), RHO_MAX_);
-  if ((est > w.rho * p.adaptive_rho_tolerance) || (est < w.rho / p.adaptive_rho_tolerance)) {
+  const double est = osqp::rho_estimate(w.rho, norm_inf<m>(w.zp), pn, norm_inf<n>(w.xp), dn);
+  if (osqp::rho_moved(est, w.rho, p.adaptive_rho_tolerance)) {
     w.rho_updates += 1;
     if (est <= 0) return 1;
-    w.rho = dmin(dmax(est, RHO_MIN_), RHO_MAX_);
+    w.rho = est;
     return factor(w);
   }
   return 0;
-}
-
-__device__ __forceinline__ bool has_solution(int s) {
-  return (s != MPCQP_STATUS_PRIMAL_INFEASIBLE) && (s != MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE) &&
-         (s != MPCQP_STATUS_DUAL_INFEASIBLE) && (s != MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE) &&
-         (s != MPCQP_STATUS_NON_CVX);
 }
 
 // orc_balance_build_qp: H (upper), g, l, u, A from one record (A1RobotControl.cpp:321-414)
@@ -405,7 +375,7 @@ __device__ __forceinline__ void build(Ws& w, const mpcqp_balance_params& bp, con
       const int row = 4 + 4 * leg + k;
       w.A[row][3 * leg + (k >> 1)] = (k & 1) ? -1.0 : 1.0;
       w.A[row][3 * leg + 2] = -bp.mu;
-      w.l[row] = -INF;
+      w.l[row] = -OSQP_INF;
       w.u[row] = 0.0;
     }
   }
@@ -529,8 +499,8 @@ __global__ void __launch_bounds__(64) balance_kernel(const double* __restrict__ 
   build(w, bp, rec);
 #pragma unroll
   for (int r = 0; r < m; ++r) {
-    w.l[r] = dmax(w.l[r], -INF);
-    w.u[r] = dmin(w.u[r], INF);
+    w.l[r] = dmax(w.l[r], -OSQP_INF);
+    w.u[r] = dmin(w.u[r], OSQP_INF);
   }
   if (p.scaling) {
     scale(w, p);
@@ -542,10 +512,9 @@ __global__ void __launch_bounds__(64) balance_kernel(const double* __restrict__ 
     for (int r = 0; r < m; ++r) w.E[r] = 1.0;
   }
   // set_rho_vec
-  w.rho = dmin(dmax(p.rho, RHO_MIN_), RHO_MAX_);
+  w.rho = dmin(dmax(p.rho, RHO_MIN), RHO_MAX);
 #pragma unroll
-  for (int r = 0; r < m; ++r)
-    w.ctype[r] = (w.l[r] < -INF * MIN_SCALING && w.u[r] > INF * MIN_SCALING) ? -1 : (w.u[r] - w.l[r] < RHO_TOL_ ? 1 : 0);
+  for (int r = 0; r < m; ++r) w.ctype[r] = osqp::row_kind(w.l[r], w.u[r]);
 #pragma unroll
   for (int j = 0; j < n; ++j) w.x[j] = 0.0;
 #pragma unroll
@@ -608,7 +577,7 @@ __global__ void __launch_bounds__(64) balance_kernel(const double* __restrict__ 
     }
   }
   if (fail) w.status = MPCQP_STATUS_NON_CVX;
-  const bool sol = has_solution(w.status);
+  const bool sol = osqp::has_solution(w.status);
   if (sol) {  // compute_obj_val
     double qf = 0.0;
 #pragma unroll
@@ -643,13 +612,7 @@ __global__ void __launch_bounds__(64) balance_kernel(const double* __restrict__ 
   }
 #pragma unroll
   for (int j = 0; j < n; ++j) res->u0[j] = xs[j];
-  res->obj_val = w.obj_val;
-  res->pri_res = w.pri_res;
-  res->dua_res = w.dua_res;
-  res->rho = w.rho;
-  res->status = w.status;
-  res->iters = w.iter;
-  res->rho_updates = w.rho_updates;
+  osqp::store_info(res, w.obj_val, w.pri_res, w.dua_res, w.rho, w.status, w.iter, w.rho_updates);
   res->nan_legs = nan_legs;
 }
 

@@ -1,6 +1,7 @@
 // mpcqp_device.h — device-side pieces shared by the dense (mpcqp_kernels.hip) and Riccati
-// (mpcqp_riccati.hip) solve kernels: OSQP constants, dimensions, cross-lane reductions and the
-// ConvexMpc condensation.  Not installed.
+// (mpcqp_riccati.hip) solve kernels: dimensions, cross-lane reductions and the ConvexMpc
+// condensation.  The OSQP constants (OSQP_INF, MIN_SCALING, RHO_MIN, ...) live in mpcqp_osqp.h with
+// the rules that use them.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -10,14 +11,11 @@
 
 #include "../../include/mpcqp.h"
 #include "mpcqp_internal.h"
+#include "mpcqp_osqp.h"
 
 namespace mpcqp {
 
 constexpr int SD = 13, ND = 12, CD = 20;
-constexpr double OSQP_INF = 1e30;
-constexpr double MIN_SCALING = 1e-4, MAX_SCALING = 1e4;
-constexpr double RHO_MIN = 1e-6, RHO_MAX = 1e6, RHO_EQ_OVER_RHO_INEQ = 1e3, RHO_TOL = 1e-4;
-constexpr double DIV_TOL = 1.0 / OSQP_INF;
 
 template <int N>
 struct Dim {

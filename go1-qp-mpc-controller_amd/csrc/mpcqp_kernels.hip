@@ -313,13 +313,7 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
       bad |= !isfinite(v);
     }
     if (__syncthreads_or(bad)) {
-      if (t0 == 0) {
-        mpcqp_result r;
-        for (int k = 0; k < ND; ++k) { r.u0[k] = NAN; r.f_body[k] = 0.0; }
-        r.obj_val = NAN; r.pri_res = NAN; r.dua_res = NAN; r.rho = p.rho;
-        r.status = MPCQP_STATUS_NAN_INPUT; r.iters = 0; r.rho_updates = 0; r.nan_legs = 0xF;
-        results[inst] = r;
-      }
+      if (t0 == 0) results[inst] = osqp::nan_input_result(p);
       if (solution)
         for (int e = t0; e < n; e += NT) solution[(size_t)inst * n + e] = NAN;
       return;
@@ -457,13 +451,8 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
   }
   const double rho0 = dmin(dmax(p.rho, RHO_MIN), RHO_MAX);
   if (row_lane) {  // set_rho_vec (auxil.c)
-    if (lo < -OSQP_INF * MIN_SCALING && hi > OSQP_INF * MIN_SCALING)
-      ct = -1;
-    else if (hi - lo < RHO_TOL)
-      ct = 1;
-    else
-      ct = 0;
-    rho_r = ct == -1 ? RHO_MIN : ct == 1 ? RHO_EQ_OVER_RHO_INEQ * rho0 : rho0;
+    ct = osqp::row_kind(lo, hi);
+    rho_r = osqp::rho_of_row(ct, rho0);
     rinv = 1. / rho_r;
     sm.rowc[r][0] = k0;
     sm.rowc[r][1] = k1;
@@ -499,7 +488,7 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
   }
   __syncthreads();
   bool need_factor = true;  // K^-1 is (re)built at the top of the iteration that needs it
-  int to_check = p.check_termination, to_adapt = p.adaptive_rho_interval;  // iter % k countdowns
+  osqp::InfoSchedule sched(p);
   for (int iter = 1; iter <= p.max_iter; ++iter) {
     const int t = opaque(threadIdx.x);
     const int f = t >> 3, tc = t & 7;
@@ -545,17 +534,8 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
       xt1 = g8_sum(e1 + o1);
       xt2 = g8_sum(e2 + o2);
     }
-    bool is_check = false, is_adapt = false;
-    if (p.check_termination && --to_check == 0) {
-      is_check = true;
-      to_check = p.check_termination;
-    }
-    if (p.adaptive_rho && --to_adapt == 0) {
-      is_adapt = true;
-      to_adapt = p.adaptive_rho_interval;
-    }
-    const bool last = iter == p.max_iter;
-    const bool need_info = is_check || is_adapt || last;
+    bool is_check, is_adapt, last;
+    const bool need_info = sched.info_step(p, iter, is_check, is_adapt, last);
     // (c) update_z / update_y on row lanes, update_x (+ P~x via the KKT identity
     //     P~x~ = rhs - sigma x~ - A~'rho A~ x~) on variable lanes
     const double kd = (k0 * xt0 + k1 * xt1) + k2 * xt2;  // row: (A~x~)_r; var: (A~'rho A~ x~)_c
@@ -617,108 +597,65 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
         put(13, var_lane ? dabs(px) : 0.0);
       }
       __syncthreads();
-      // workgroup maxima read from LDS where they are used (not held across the check)
+      // workgroup maxima, merged where OSQP takes the max of several norms
       auto mx = [&](int k) {
         double v = sm.info[0][k];
         for (int w = 1; w < Dm::NW; ++w) v = dmax(v, sm.info[w][k]);
         return v;
       };
+      const osqp::Norms nm = {mx(0), mx(1), dmax(mx(2), mx(4)), dmax(mx(3), mx(5)),
+                              mx(6), mx(7), dmax(dmax(mx(8), mx(10)), mx(12)), dmax(dmax(mx(9), mx(11)), mx(13))};
       const double cost_c = sm.cst[0], cinv = 1. / cost_c;
       double rho = sm.cst[1];
-      const double pri_res = mx(0);
-      const double dua_res = cinv * mx(6);
+      const double pri_res = nm.pri;
+      const double dua_res = cinv * nm.dua;
       iters = iter;
       // check_termination (osqp.c): approx=1 is the post-loop check at max_iter (eps x 10)
       auto check = [&](bool approx) -> int {
-        double eps_abs = p.eps_abs, eps_rel = p.eps_rel, eps_pinf = p.eps_prim_inf, eps_dinf = p.eps_dual_inf;
-        if (pri_res > OSQP_INF || dua_res > OSQP_INF) return MPCQP_STATUS_NON_CVX;
-        if (approx) { eps_abs *= 10; eps_rel *= 10; eps_pinf *= 10; eps_dinf *= 10; }
-        const double eps_prim = eps_abs + eps_rel * dmax(mx(2), mx(4));
-        const bool prim_ok = pri_res < eps_prim;
-        bool prim_inf = false, dual_inf = false;
-        if (!prim_ok) {
-          // is_primal_infeasible: project delta_y onto the polar of the recession cone (in place)
-          if (row_lane) {
-            if (hi > OSQP_INF * MIN_SCALING) {
-              if (lo < -OSQP_INF * MIN_SCALING) dyv = 0.0;
-              else dyv = dmin(dyv, 0.0);
-            } else if (lo < -OSQP_INF * MIN_SCALING) {
-              dyv = dmax(dyv, 0.0);
-            }
-          }
-          double nd[1] = {row_lane ? dabs(E * dyv) : 0.0};
-          wg_reduce<N, 1, true>(sm, nd, rslot);
-          const double ndy = nd[0];
-          if (ndy > DIV_TOL) {
-            double lh[1] = {row_lane ? hi * dmax(dyv, 0.0) + lo * dmin(dyv, 0.0) : 0.0};
-            wg_reduce<N, 1, false>(sm, lh, rslot);
-            if (lh[0] < eps_pinf * ndy) {
+        return osqp::check_termination(
+            p, approx, nm, cinv,
+            [&](double eps_pinf) -> bool {
+              // is_primal_infeasible: project delta_y onto the polar of the recession cone (in place)
+              if (row_lane) dyv = osqp::polar_project(dyv, lo, hi);
+              double nd[1] = {row_lane ? dabs(E * dyv) : 0.0};
+              wg_reduce<N, 1, true>(sm, nd, rslot);
+              const double ndy = nd[0];
+              if (!(ndy > DIV_TOL)) return false;
+              double lh[1] = {row_lane ? hi * dmax(dyv, 0.0) + lo * dmin(dyv, 0.0) : 0.0};
+              wg_reduce<N, 1, false>(sm, lh, rslot);
+              if (!(lh[0] < eps_pinf * ndy)) return false;
               const double atd = gather_atv(row_lane ? km * dyv : 0.0, row_lane ? kz * dyv : 0.0, a, 0.0);
               double an[1] = {var_lane ? dabs(Di * atd) : 0.0};
               wg_reduce<N, 1, true>(sm, an, rslot);
-              prim_inf = an[0] < eps_pinf * ndy;
-            }
-          }
-        }
-        const double eps_dual = eps_abs + eps_rel * (cinv * dmax(dmax(mx(8), mx(10)), mx(12)));
-        const bool dual_ok = dua_res < eps_dual;
-        if (!dual_ok) {
-          // is_dual_infeasible (P~ delta_x = P~x_new - P~x_old)
-          double nx[1] = {var_lane ? dabs(D * dxv) : 0.0};
-          wg_reduce<N, 1, true>(sm, nx, rslot);
-          const double ndx = nx[0];
-          if (ndx > DIV_TOL) {
-            double qd[1] = {var_lane ? q * dxv : 0.0};
-            wg_reduce<N, 1, false>(sm, qd, rslot);
-            if (qd[0] < cost_c * eps_dinf * ndx) {
+              return an[0] < eps_pinf * ndy;
+            },
+            [&](double eps_dinf) -> bool {
+              // is_dual_infeasible (P~ delta_x = P~x_new - P~x_old)
+              double nx[1] = {var_lane ? dabs(D * dxv) : 0.0};
+              wg_reduce<N, 1, true>(sm, nx, rslot);
+              const double ndx = nx[0];
+              if (!(ndx > DIV_TOL)) return false;
+              double qd[1] = {var_lane ? q * dxv : 0.0};
+              wg_reduce<N, 1, false>(sm, qd, rslot);
+              if (!(qd[0] < cost_c * eps_dinf * ndx)) return false;
               double pd[1] = {var_lane ? dabs(Di * (px - pxo)) : 0.0};
               wg_reduce<N, 1, true>(sm, pd, rslot);
-              if (pd[0] < cost_c * eps_dinf * ndx) {
-                const double dx0 = __shfl(dxv, gb + 5), dx1 = __shfl(dxv, gb + 6), dx2 = __shfl(dxv, gb + 7);
-                double viol = 0.0;
-                if (row_lane) {
-                  const double v = Ei * ((k0 * dx0 + k1 * dx1) + k2 * dx2);
-                  if ((hi < OSQP_INF * MIN_SCALING && v > eps_dinf * ndx) ||
-                      (lo > -OSQP_INF * MIN_SCALING && v < -eps_dinf * ndx))
-                    viol = 1.0;
-                }
-                double vv[1] = {viol};
-                wg_reduce<N, 1, true>(sm, vv, rslot);
-                dual_inf = vv[0] == 0.0;
+              if (!(pd[0] < cost_c * eps_dinf * ndx)) return false;
+              const double dx0 = __shfl(dxv, gb + 5), dx1 = __shfl(dxv, gb + 6), dx2 = __shfl(dxv, gb + 7);
+              double viol = 0.0;
+              if (row_lane) {
+                const double v = Ei * ((k0 * dx0 + k1 * dx1) + k2 * dx2);
+                if (osqp::dual_ray_violates(v, lo, hi, eps_dinf * ndx)) viol = 1.0;
               }
-            }
-          }
-        }
-        if (prim_ok && dual_ok) return approx ? MPCQP_STATUS_SOLVED_INACCURATE : MPCQP_STATUS_SOLVED;
-        if (prim_inf) return approx ? MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_PRIMAL_INFEASIBLE;
-        if (dual_inf) return approx ? MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_DUAL_INFEASIBLE;
-        return MPCQP_STATUS_UNSOLVED;
+              double vv[1] = {viol};
+              wg_reduce<N, 1, true>(sm, vv, rslot);
+              return vv[0] == 0.0;
+            });
       };
-      int st = MPCQP_STATUS_UNSOLVED;
-      bool done = false, refactor = false;
-      for (int pass = 0; pass < 2 && !done; ++pass) {
-        // pass 0: in-loop check_termination; pass 1: osqp_solve's approximate check at max_iter
-        if (pass == 1 && !last) break;
-        if (pass == 1 || is_check || last) {
-          st = check(pass == 1);
-          done = st != MPCQP_STATUS_UNSOLVED;
-        }
-        if (pass == 1 || done || !is_adapt) continue;
-        // adapt_rho / compute_rho_estimate (scaled residuals and norms); runs before the
-        // post-loop approximate check of osqp_solve
-        const double pr_n = mx(1) / (dmax(mx(3), mx(5)) + DIV_TOL);
-        const double du_n = mx(7) / (dmax(dmax(mx(9), mx(11)), mx(13)) + DIV_TOL);
-        double est = rho * sqrt(pr_n / (du_n + DIV_TOL));
-        est = dmin(dmax(est, RHO_MIN), RHO_MAX);
-        if (est > rho * p.adaptive_rho_tolerance || est < rho / p.adaptive_rho_tolerance) {
-          rho = dmin(dmax(est, RHO_MIN), RHO_MAX);
-          rho_updates += 1;
-          refactor = !last;
-        }
-      }
-      if (last && st == MPCQP_STATUS_UNSOLVED) st = MPCQP_STATUS_MAX_ITER_REACHED;
-      if (last) done = true;
-      status = st;
+      // adapt_rho runs before osqp_solve's approximate check at max_iter
+      const osqp::Verdict vd = osqp::info_iteration(p, is_check, is_adapt, last, nm, rho, rho_updates, check);
+      const bool done = vd.status != MPCQP_STATUS_UNSOLVED, refactor = vd.refactor;
+      status = vd.status;
 #ifdef MPCQP_PHASE_TIMING
       if (is_check) PHASE_MARK(30);
 #else
@@ -738,8 +675,7 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
         // osqp_update_rho: new rho vector and A~'rho A~ blocks now; P~ reload + re-inversion at
         // the top of the next iteration
         if (row_lane) {
-          const int ct = (int)parkc[11];
-          rho_r = ct == -1 ? rho_r : ct == 1 ? RHO_EQ_OVER_RHO_INEQ * rho : rho;
+          rho_r = osqp::rho_of_row((int)parkc[11], rho);
           rinv = 1. / rho_r;
           sm.rowc[5 * f + tc][3] = rho_r;
         }
@@ -775,10 +711,7 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
   // ---- 4. store_solution + unscale + compute_grf extraction (A1RobotControl.cpp:555-561) ------
   __syncthreads();
   const double cinv = 1. / sm.cst[0], rho = sm.cst[1], pri_res = sm.cst[2], dua_res = sm.cst[3];
-  const bool has_sol = status != MPCQP_STATUS_PRIMAL_INFEASIBLE &&
-                       status != MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE &&
-                       status != MPCQP_STATUS_DUAL_INFEASIBLE &&
-                       status != MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE && status != MPCQP_STATUS_NON_CVX;
+  const bool has_sol = osqp::has_solution(status);
   {
     // objective 1/2 x'P~x + q~'x (unscaled by cinv)
     double ob[1] = {var_lane ? 0.5 * x * px + q * x : 0.0};
@@ -805,18 +738,8 @@ __global__ __launch_bounds__(Dim<N>::NT) void solve_kernel(
         int legs = 0;
         for (int l = 0; l < 4; ++l) legs |= ((nb >> (8 * l)) & 1ull) ? (1 << l) : 0;
         res->nan_legs = legs;
-        double obj;
-        if (has_sol) obj = ob[0] * cinv;
-        else if (status == MPCQP_STATUS_PRIMAL_INFEASIBLE || status == MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE) obj = OSQP_INF;
-        else if (status == MPCQP_STATUS_DUAL_INFEASIBLE || status == MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE) obj = -OSQP_INF;
-        else obj = NAN;
-        res->obj_val = obj;
-        res->pri_res = pri_res;
-        res->dua_res = dua_res;
-        res->rho = rho;
-        res->status = status;
-        res->iters = iters;
-        res->rho_updates = rho_updates;
+        osqp::store_info(res, osqp::objective_of(status, ob[0], cinv), pri_res, dua_res, rho, status, iters,
+                         rho_updates);
       }
     }
   }

@@ -309,13 +309,7 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
       bad |= !isfinite(v);
     }
     if (__syncthreads_or(bad)) {
-      if (t == 0) {
-        mpcqp_result r;
-        for (int k = 0; k < ND; ++k) { r.u0[k] = NAN; r.f_body[k] = 0.0; }
-        r.obj_val = NAN; r.pri_res = NAN; r.dua_res = NAN; r.rho = p.rho;
-        r.status = MPCQP_STATUS_NAN_INPUT; r.iters = 0; r.rho_updates = 0; r.nan_legs = 0xF;
-        results[inst] = r;
-      }
+      if (t == 0) results[inst] = osqp::nan_input_result(p);
       if (solution)
         for (int e = t; e < n; e += NT) solution[(size_t)inst * n + e] = NAN;
       return;
@@ -421,12 +415,9 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
     const double l = E * sm.lo[r], u = E * sm.hi[r];
     sm.lo[r] = l;
     sm.hi[r] = u;
-    int ct;
-    if (l < -OSQP_INF * MIN_SCALING && u > OSQP_INF * MIN_SCALING) ct = -1;
-    else if (u - l < RHO_TOL) ct = 1;
-    else ct = 0;
+    const int ct = osqp::row_kind(l, u);
     sm.ctype[r] = ct;
-    sm.rho_v[r] = ct == -1 ? RHO_MIN : ct == 1 ? RHO_EQ_OVER_RHO_INEQ * rho0 : rho0;
+    sm.rho_v[r] = osqp::rho_of_row(ct, rho0);
     sm.rho_inv[r] = 1. / sm.rho_v[r];
     sm.z[r] = 0.0;
     sm.y[r] = 0.0;
@@ -451,7 +442,7 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
   // ---- 3. ADMM ----
   int status = MPCQP_STATUS_UNSOLVED, iters = 0, rho_updates = 0, ntrace = 0;
   bool need_factor = true;
-  int to_check = p.check_termination, to_adapt = p.adaptive_rho_interval;
+  osqp::InfoSchedule sched(p);
   for (int iter = 1; iter <= p.max_iter; ++iter) {
     if (need_factor) {
       factorize<N>(sm, p, sigma);
@@ -463,17 +454,8 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
       for (int c = t; c < n; c += 64) sm.uo[c] = (1.0 / sm.D[c]) * sm.uo[c];
     }
     __syncthreads();
-    bool is_check = false, is_adapt = false;
-    if (p.check_termination && --to_check == 0) {
-      is_check = true;
-      to_check = p.check_termination;
-    }
-    if (p.adaptive_rho && --to_adapt == 0) {
-      is_adapt = true;
-      to_adapt = p.adaptive_rho_interval;
-    }
-    const bool last = iter == p.max_iter;
-    const bool need_info = is_check || is_adapt || last;
+    bool is_check, is_adapt, last;
+    const bool need_info = sched.info_step(p, iter, is_check, is_adapt, last);
     // per-foot updates: update_z / update_y (rows), update_x + P~x by the KKT identity (vars);
     // delta y, delta x and the previous P~x are kept for the infeasibility tests
     for (int f = t; f < nf; f += NT) {
@@ -553,36 +535,29 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
         for (int w = 1; w < NWV; ++w) v = dmax(v, sm.info[w][k]);
         return v;
       };
-      const double pri_res = mx(0);
-      const double dua_res = cinv * mx(6);
+      // merged where OSQP takes the max of several norms
+      const osqp::Norms nm = {mx(0), mx(1), dmax(mx(2), mx(4)), dmax(mx(3), mx(5)),
+                              mx(6), mx(7), dmax(dmax(mx(8), mx(10)), mx(12)), dmax(dmax(mx(9), mx(11)), mx(13))};
+      const double pri_res = nm.pri;
+      const double dua_res = cinv * nm.dua;
       iters = iter;
       // check_termination (osqp.c): approx=1 is the post-loop check at max_iter (eps x 10)
       auto check = [&](bool approx) __attribute__((always_inline)) -> int {
-        double eps_abs = p.eps_abs, eps_rel = p.eps_rel, eps_pinf = p.eps_prim_inf, eps_dinf = p.eps_dual_inf;
-        if (pri_res > OSQP_INF || dua_res > OSQP_INF) return MPCQP_STATUS_NON_CVX;
-        if (approx) { eps_abs *= 10; eps_rel *= 10; eps_pinf *= 10; eps_dinf *= 10; }
-        const double eps_prim = eps_abs + eps_rel * dmax(mx(2), mx(4));
-        const bool prim_ok = pri_res < eps_prim;
-        bool prim_inf = false, dual_inf = false;
-        if (!prim_ok) {
-          // is_primal_infeasible: project delta_y onto the polar of the recession cone (in place)
-          double nd = 0.0, lh = 0.0;
-          for (int r = t; r < m; r += NT) {
-            double d = sm.dy[r];
-            if (sm.hi[r] > OSQP_INF * MIN_SCALING) {
-              if (sm.lo[r] < -OSQP_INF * MIN_SCALING) d = 0.0;
-              else d = dmin(d, 0.0);
-            } else if (sm.lo[r] < -OSQP_INF * MIN_SCALING) {
-              d = dmax(d, 0.0);
-            }
-            sm.dy[r] = d;
-            nd = dmax(nd, dabs(sm.E[r] * d));
-            lh += sm.hi[r] * dmax(d, 0.0) + sm.lo[r] * dmin(d, 0.0);
-          }
-          const double ndy = wg_red1<RSmem<N>, true>(sm, nd, rslot);
-          if (ndy > DIV_TOL) {
-            lh = wg_red1<RSmem<N>, false>(sm, lh, rslot);
-            if (lh < eps_pinf * ndy) {
+        return osqp::check_termination(
+            p, approx, nm, cinv,
+            [&](double eps_pinf) __attribute__((always_inline)) -> bool {
+              // is_primal_infeasible: project delta_y onto the polar of the recession cone (in place)
+              double nd = 0.0, lh = 0.0;
+              for (int r = t; r < m; r += NT) {
+                const double d = osqp::polar_project(sm.dy[r], sm.lo[r], sm.hi[r]);
+                sm.dy[r] = d;
+                nd = dmax(nd, dabs(sm.E[r] * d));
+                lh += sm.hi[r] * dmax(d, 0.0) + sm.lo[r] * dmin(d, 0.0);
+              }
+              const double ndy = wg_red1<RSmem<N>, true>(sm, nd, rslot);
+              if (!(ndy > DIV_TOL)) return false;
+              lh = wg_red1<RSmem<N>, false>(sm, lh, rslot);
+              if (!(lh < eps_pinf * ndy)) return false;
               double an = 0.0;
               for (int c = t; c < n; c += NT) {
                 const int f = c / 3, a = c % 3;
@@ -591,70 +566,38 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
                 an = dmax(an, dabs((1.0 / sm.D[c]) * atd));
               }
               an = wg_red1<RSmem<N>, true>(sm, an, rslot);
-              prim_inf = an < eps_pinf * ndy;
-            }
-          }
-        }
-        const double eps_dual = eps_abs + eps_rel * (cinv * dmax(dmax(mx(8), mx(10)), mx(12)));
-        const bool dual_ok = dua_res < eps_dual;
-        if (!dual_ok) {
-          // is_dual_infeasible (P~ delta_x = P~x_new - P~x_old)
-          double nx = 0.0, qd = 0.0;
-          for (int c = t; c < n; c += NT) {
-            nx = dmax(nx, dabs(sm.D[c] * sm.Dt[c]));
-            qd += sm.q[c] * sm.Dt[c];
-          }
-          const double ndx = wg_red1<RSmem<N>, true>(sm, nx, rslot);
-          if (ndx > DIV_TOL) {
-            qd = wg_red1<RSmem<N>, false>(sm, qd, rslot);
-            if (qd < cost_c * eps_dinf * ndx) {
+              return an < eps_pinf * ndy;
+            },
+            [&](double eps_dinf) __attribute__((always_inline)) -> bool {
+              // is_dual_infeasible (P~ delta_x = P~x_new - P~x_old)
+              double nx = 0.0, qd = 0.0;
+              for (int c = t; c < n; c += NT) {
+                nx = dmax(nx, dabs(sm.D[c] * sm.Dt[c]));
+                qd += sm.q[c] * sm.Dt[c];
+              }
+              const double ndx = wg_red1<RSmem<N>, true>(sm, nx, rslot);
+              if (!(ndx > DIV_TOL)) return false;
+              qd = wg_red1<RSmem<N>, false>(sm, qd, rslot);
+              if (!(qd < cost_c * eps_dinf * ndx)) return false;
               double pd = 0.0;
               for (int c = t; c < n; c += NT) pd = dmax(pd, dabs((1.0 / sm.D[c]) * (sm.px[c] - sm.colmax[c])));
               pd = wg_red1<RSmem<N>, true>(sm, pd, rslot);
-              if (pd < cost_c * eps_dinf * ndx) {
-                double viol = 0.0;
-                for (int r = t; r < m; r += NT) {
-                  const int f = r / 5;
-                  const double adx =
-                      (sm.ak[r][0] * sm.Dt[3 * f] + sm.ak[r][1] * sm.Dt[3 * f + 1]) + sm.ak[r][2] * sm.Dt[3 * f + 2];
-                  const double v = (1.0 / sm.E[r]) * adx;
-                  if ((sm.hi[r] < OSQP_INF * MIN_SCALING && v > eps_dinf * ndx) ||
-                      (sm.lo[r] > -OSQP_INF * MIN_SCALING && v < -eps_dinf * ndx))
-                    viol = 1.0;
-                }
-                viol = wg_red1<RSmem<N>, true>(sm, viol, rslot);
-                dual_inf = viol == 0.0;
+              if (!(pd < cost_c * eps_dinf * ndx)) return false;
+              double viol = 0.0;
+              for (int r = t; r < m; r += NT) {
+                const int f = r / 5;
+                const double adx =
+                    (sm.ak[r][0] * sm.Dt[3 * f] + sm.ak[r][1] * sm.Dt[3 * f + 1]) + sm.ak[r][2] * sm.Dt[3 * f + 2];
+                const double v = (1.0 / sm.E[r]) * adx;
+                if (osqp::dual_ray_violates(v, sm.lo[r], sm.hi[r], eps_dinf * ndx)) viol = 1.0;
               }
-            }
-          }
-        }
-        if (prim_ok && dual_ok) return approx ? MPCQP_STATUS_SOLVED_INACCURATE : MPCQP_STATUS_SOLVED;
-        if (prim_inf) return approx ? MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_PRIMAL_INFEASIBLE;
-        if (dual_inf) return approx ? MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_DUAL_INFEASIBLE;
-        return MPCQP_STATUS_UNSOLVED;
+              viol = wg_red1<RSmem<N>, true>(sm, viol, rslot);
+              return viol == 0.0;
+            });
       };
-      int st = MPCQP_STATUS_UNSOLVED;
-      bool done = false, refactor = false;
-      for (int pass = 0; pass < 2 && !done; ++pass) {
-        if (pass == 1 && !last) break;
-        if (pass == 1 || is_check || last) {
-          st = check(pass == 1);
-          done = st != MPCQP_STATUS_UNSOLVED;
-        }
-        if (pass == 1 || done || !is_adapt) continue;
-        const double pr_n = mx(1) / (dmax(mx(3), mx(5)) + DIV_TOL);
-        const double du_n = mx(7) / (dmax(dmax(mx(9), mx(11)), mx(13)) + DIV_TOL);
-        double est = rho * sqrt(pr_n / (du_n + DIV_TOL));
-        est = dmin(dmax(est, RHO_MIN), RHO_MAX);
-        if (est > rho * p.adaptive_rho_tolerance || est < rho / p.adaptive_rho_tolerance) {
-          rho = dmin(dmax(est, RHO_MIN), RHO_MAX);
-          rho_updates += 1;
-          refactor = !last;
-        }
-      }
-      if (last && st == MPCQP_STATUS_UNSOLVED) st = MPCQP_STATUS_MAX_ITER_REACHED;
-      if (last) done = true;
-      status = st;
+      const osqp::Verdict vd = osqp::info_iteration(p, is_check, is_adapt, last, nm, rho, rho_updates, check);
+      const bool done = vd.status != MPCQP_STATUS_UNSOLVED, refactor = vd.refactor;
+      status = vd.status;
       if (trace && t == 0 && inst < trace_cap && ntrace < MPCQP_TRACE_LEN && is_check) {
         double* tp = trace + ((size_t)inst * MPCQP_TRACE_LEN + ntrace) * 4;
         tp[0] = iter; tp[1] = pri_res; tp[2] = dua_res; tp[3] = rho;
@@ -669,8 +612,7 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
       if (done) break;
       if (refactor) {
         for (int r = t; r < m; r += NT) {
-          const int ct = sm.ctype[r];
-          sm.rho_v[r] = ct == -1 ? sm.rho_v[r] : ct == 1 ? RHO_EQ_OVER_RHO_INEQ * rho : rho;
+          sm.rho_v[r] = osqp::rho_of_row(sm.ctype[r], rho);
           sm.rho_inv[r] = 1. / sm.rho_v[r];
         }
         __syncthreads();
@@ -697,10 +639,7 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
 
   // ---- 4. store_solution + unscale + compute_grf extraction (A1RobotControl.cpp:555-561) ----
   const double cinv = 1. / sm.cst[0], rho = sm.cst[1], pri_res = sm.cst[2], dua_res = sm.cst[3];
-  const bool has_sol = status != MPCQP_STATUS_PRIMAL_INFEASIBLE &&
-                       status != MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE &&
-                       status != MPCQP_STATUS_DUAL_INFEASIBLE &&
-                       status != MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE && status != MPCQP_STATUS_NON_CVX;
+  const bool has_sol = osqp::has_solution(status);
   double ob = 0.0;
   for (int c = t; c < n; c += NT) ob += 0.5 * sm.x[c] * sm.px[c] + sm.q[c] * sm.x[c];
   ob = wg_red1<RSmem<N>, false>(sm, ob, rslot);
@@ -729,18 +668,7 @@ __global__ __launch_bounds__(NT) void ric_solve_kernel(const double* __restrict_
       }
     }
     res->nan_legs = legs;
-    double obj;
-    if (has_sol) obj = ob * cinv;
-    else if (status == MPCQP_STATUS_PRIMAL_INFEASIBLE || status == MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE) obj = OSQP_INF;
-    else if (status == MPCQP_STATUS_DUAL_INFEASIBLE || status == MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE) obj = -OSQP_INF;
-    else obj = NAN;
-    res->obj_val = obj;
-    res->pri_res = pri_res;
-    res->dua_res = dua_res;
-    res->rho = rho;
-    res->status = status;
-    res->iters = iters;
-    res->rho_updates = rho_updates;
+    osqp::store_info(res, osqp::objective_of(status, ob, cinv), pri_res, dua_res, rho, status, iters, rho_updates);
   }
 }
 

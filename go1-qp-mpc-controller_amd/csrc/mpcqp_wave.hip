@@ -125,13 +125,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
       bad |= !isfinite(v);
     }
     if (__ballot(bad) != 0) {
-      if (t == 0) {
-        mpcqp_result r;
-        for (int k = 0; k < ND; ++k) { r.u0[k] = NAN; r.f_body[k] = 0.0; }
-        r.obj_val = NAN; r.pri_res = NAN; r.dua_res = NAN; r.rho = p.rho;
-        r.status = MPCQP_STATUS_NAN_INPUT; r.iters = 0; r.rho_updates = 0; r.nan_legs = 0xF;
-        results[inst] = r;
-      }
+      if (t == 0) results[inst] = osqp::nan_input_result(p);
       if (solution)
         for (int e = t; e < n; e += NT) solution[(size_t)inst * n + e] = NAN;
       return 0;
@@ -277,6 +271,8 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
       Z4[r] = AK4[r] * xz;
     }
   }
+  // osqp::rho_of_row(osqp::row_kind(l4, u4), rho), written out: through the int row class the
+  // compiler schedules the setup differently (rows 0-3 are always inequalities: rho itself)
   auto rho4_of = [&](double l4, double u4, double rho) __attribute__((always_inline)) {
     const bool loose = l4 < -OSQP_INF * MIN_SCALING && u4 > OSQP_INF * MIN_SCALING;
     const bool eq = u4 - l4 < RHO_TOL;
@@ -465,7 +461,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
   int status = MPCQP_STATUS_UNSOLVED, iters = 0, rho_updates = 0, ntrace = 0;
   double obj_sum = 0.0;  // 1/2 x'P~x + q~'x of the final iterate (scaled), set when the loop ends
   bool need_factor = true;
-  int to_check = p.check_termination, to_adapt = p.adaptive_rho_interval;
+  osqp::InfoSchedule sched(p);
   bool amp_bad = false;  // the Schur form's cancellation bound was crossed at the last check
   for (int iter = 1; iter <= p.max_iter; ++iter) {
     if (need_factor) {
@@ -668,20 +664,10 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
       // LDS operands are loaded one phase ahead of their use; sched_barrier keeps the scheduler from
       // sinking a prefetch back down to its consumer (counted lgkmcnt waits then cover only it).
       double W[R], AKw[R], SMv[R], G[R], Hh[R], XS[R], tt[R];
-      // Up to three rounds every phase's rows of all rounds are loaded one phase ahead (48 R VGPRs);
-      // beyond, each phase streams its rounds through two 12-double buffers.
-      constexpr bool PF = R <= 3;
-      double cA[PF ? R : 1][12], cB[PF ? R : 1][12], cw[PF ? R : 1][3];
-      // stream the rounds of a parallel phase: load(r, c) fills c with round r's rows, use(r, c)
-      auto pipe = [&](auto load, auto use) __attribute__((always_inline)) {
-        double c0[12], c1[12];
-        load(0, c0);
-        sfor<0, R>([&](auto RR) {
-          constexpr int r = decltype(RR)::value;
-          if constexpr (r + 1 < R) load(r + 1, (r & 1) ? c0 : c1);
-          use(r, (r & 1) ? c1 : c0);
-        });
-      };
+      // Every phase's rows of all rounds are loaded one phase ahead (48 R VGPRs): Acl is stored only
+      // up to ACL_MAXN steps, three rounds.
+      static_assert(R <= 3, "the stored-Acl solve holds every round's rows in registers");
+      double cA[R][12], cB[R][12], cw[R][3];
       int kc[R], kk[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -692,10 +678,8 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
         kk[r] = max(kc[r] - 1, 0);  // slot of K_k (k >= 1)
       }
       double cn[12];
-      if constexpr (PF) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) ldcol(cA[r], &F.K[kk[r]][idx]);
-      }
+      for (int r = 0; r < R; ++r) ldcol(cA[r], &F.K[kk[r]][idx]);
       // The chains load Acl one ROUND at a time: DPP row q takes the matrix of step 4 rr + gray(q) of
       // round rr, the step that row computes (every chain step runs in the row of its step), so one
       // 12-double load per lane serves four chain steps.
@@ -704,28 +688,20 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
       if constexpr (N >= 3) ldcol(cn, &F.Acl[aslot((N - 2) >> 2)][idx]);
       __builtin_amdgcn_sched_barrier(0);
       // a_k = K_k' w_k (k >= 1)
-      if constexpr (PF) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) lds_wait<N >= 3 ? 12 : 0>(cA[r]);
-        mv_rounds<R>(W, cA, AKw);
-      } else {
-        lds_wait<0>(cn);  // (the chain's first columns; the streamed loads below are compiler-tracked)
-        pipe([&](int r, double (&c)[12]) __attribute__((always_inline)) { ld12s(c, &F.K[kk[r]][idx]); },
-             [&](int r, const double (&c)[12]) __attribute__((always_inline)) { AKw[r] = mv12(W[r], c); });
-      }
+      for (int r = 0; r < R; ++r) lds_wait<N >= 3 ? 12 : 0>(cA[r]);
+      mv_rounds<R>(W, cA, AKw);
       __builtin_amdgcn_sched_barrier(0);
       if (tm_it) WV_MARK(41);
       // g_k's G_k^-1 rows and B_k' columns: issued when the backward chain enters its last round
       // (three steps before their use), so they do not hold registers through the whole chain
       auto load_g = [&]() __attribute__((always_inline)) {
-        if constexpr (PF) {
 #pragma unroll
-          for (int r = 0; r < R; ++r) {
-            ld12(cB[r], &F.Gi[kc[r]][mo(idx)]);
-            cw[r][0] = sm.Bw[kc[r]][0][idx];
-            cw[r][1] = sm.Bw[kc[r]][1][idx];
-            cw[r][2] = sm.Bw[kc[r]][2][idx];
-          }
+        for (int r = 0; r < R; ++r) {
+          ld12(cB[r], &F.Gi[kc[r]][mo(idx)]);
+          cw[r][0] = sm.Bw[kc[r]][0][idx];
+          cw[r][1] = sm.Bw[kc[r]][1][idx];
+          cw[r][2] = sm.Bw[kc[r]][2][idx];
         }
       };
       constexpr int KG = N - 2 >= 2 ? 2 : N - 2;  // the backward chain's step that issues them
@@ -762,36 +738,25 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
         const double ls = dtm * legsum(G[r]);
         return leg == 2 ? hb : (leg == 3 ? ls : 0.0);
       };
-      if constexpr (PF) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) tt[r] = ttr(r, cw[r][0], cw[r][1], cw[r][2]);
+      for (int r = 0; r < R; ++r) tt[r] = ttr(r, cw[r][0], cw[r][1], cw[r][2]);
 #pragma unroll
-        for (int r = 0; r < R; ++r) ld12(cA[r], &sm.Bw[kc[r]][av ? a : 2][0]);  // for h_k
-        __builtin_amdgcn_sched_barrier(0);
-        mv_rounds<R>(tt, cB, G);
-        if constexpr (N >= 3) ld12(cn, &F.Acl[aslot(0)][mo(idx)]);
-        __builtin_amdgcn_sched_barrier(0);
+      for (int r = 0; r < R; ++r) ld12(cA[r], &sm.Bw[kc[r]][av ? a : 2][0]);  // for h_k
+      __builtin_amdgcn_sched_barrier(0);
+      mv_rounds<R>(tt, cB, G);
+      if constexpr (N >= 3) ld12(cn, &F.Acl[aslot(0)][mo(idx)]);
+      __builtin_amdgcn_sched_barrier(0);
+      {
         double hb[R];
         mv_rounds<R>(G, cA, hb);
 #pragma unroll
         for (int r = 0; r < R; ++r) Hh[r] = hhr(r, hb[r]);
-      } else {
-        pipe([&](int r, double (&c)[12]) __attribute__((always_inline)) { ld12(c, &F.Gi[kc[r]][mo(idx)]); },
-             [&](int r, const double (&c)[12]) __attribute__((always_inline)) {
-               tt[r] = ttr(r, sm.Bw[kc[r]][0][idx], sm.Bw[kc[r]][1][idx], sm.Bw[kc[r]][2][idx]);
-               G[r] = mv12(tt[r], c);
-             });
-        pipe([&](int r, double (&c)[12]) __attribute__((always_inline)) { ld12(c, &sm.Bw[kc[r]][av ? a : 2][0]); },
-             [&](int r, const double (&c)[12]) __attribute__((always_inline)) { Hh[r] = hhr(r, mv12(G[r], c)); });
-        if constexpr (N >= 3) ld12(cn, &F.Acl[aslot(0)][mo(idx)]);
       }
       if (tm_it) WV_MARK(43);
       // u_k's K_k rows: issued three steps before the forward chain ends
       auto load_u = [&]() __attribute__((always_inline)) {
-        if constexpr (PF) {
 #pragma unroll
-          for (int r = 0; r < R; ++r) ld12(cB[r], &F.K[kk[r]][mo(idx)]);
-        }
+        for (int r = 0; r < R; ++r) ld12(cB[r], &F.K[kk[r]][mo(idx)]);
       };
       constexpr int KU = N - 2 >= 1 ? (N - 3 > 1 ? N - 3 : 1) : 0;  // two steps before the end
       if constexpr (KU < 1) load_u();
@@ -816,15 +781,10 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
       }
       if (tm_it) WV_MARK(44);
       // u_k = g_k - K_k x_k (x_0 = 0)
-      if constexpr (PF) {
-        double kx[R];
-        mv_rounds<R>(XS, cB, kx);
+      double kx[R];
+      mv_rounds<R>(XS, cB, kx);
 #pragma unroll
-        for (int r = 0; r < R; ++r) U[r] = G[r] - kx[r];
-      } else {
-        pipe([&](int r, double (&c)[12]) __attribute__((always_inline)) { ld12(c, &F.K[kk[r]][mo(idx)]); },
-             [&](int r, const double (&c)[12]) __attribute__((always_inline)) { U[r] = G[r] - mv12(XS[r], c); });
-      }
+      for (int r = 0; r < R; ++r) U[r] = G[r] - kx[r];
     }
     if (tm_it) WV_MARK(45);
     };  // kkt
@@ -889,13 +849,10 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
     // step or the last iteration) run in a loop of their own: the check's registers are then live
     // only outside it, and the allocator keeps the ADMM state of the inner loop in registers.
     {
-      int plain = p.max_iter - iter;
-      if (p.check_termination) plain = min(plain, to_check - 1);
-      if (p.adaptive_rho) plain = min(plain, to_adapt - 1);
+      const int plain = sched.plain_ahead(p, iter);
       for (int j = 0; j < plain; ++j) {
         kkt(IC<0>{});
-        if (p.check_termination) --to_check;
-        if (p.adaptive_rho) --to_adapt;
+        sched.plain_step(p);
         update(IC<0>{});
         if (iter == 60) WV_MARK(46);
         if (iter == 60) WV_MARK(47);
@@ -904,17 +861,8 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
     }
     const bool tm_it = iter == 60;
     kkt(IC<1>{});  // (with the inner loop above, always an update_info iteration)
-    bool is_check = false, is_adapt = false;
-    if (p.check_termination && --to_check == 0) {
-      is_check = true;
-      to_check = p.check_termination;
-    }
-    if (p.adaptive_rho && --to_adapt == 0) {
-      is_adapt = true;
-      to_adapt = p.adaptive_rho_interval;
-    }
-    const bool last = iter == p.max_iter;
-    const bool need_info = is_check || is_adapt || last;
+    bool is_check, is_adapt, last;
+    const bool need_info = sched.info_step(p, iter, is_check, is_adapt, last);
 
     if (need_info) update(IC<1>{});
     else update(IC<0>{});
@@ -974,16 +922,6 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
 #pragma unroll
       for (int k = 0; k < NM; ++k) mx[k] = 0.0;
       double nd = 0.0, lh = 0.0, nx = 0.0, qd = 0.0, dyp[R], dyp4[R];
-      auto proj = [&](double d, double lo, double hi) __attribute__((always_inline)) {
-        // delta_y projected onto the polar of the recession cone of [l, u]
-        if (hi > OSQP_INF * MIN_SCALING) {
-          if (lo < -OSQP_INF * MIN_SCALING) d = 0.0;
-          else d = dmin(d, 0.0);
-        } else if (lo < -OSQP_INF * MIN_SCALING) {
-          d = dmax(d, 0.0);
-        }
-        return d;
-      };
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const double xp = dpp<QP_PRIM>(X[r]), xz = dpp<QP_B2>(X[r]);
@@ -1007,7 +945,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
         }
         // is_primal_infeasible: ||E dy||_inf and u'max(dy, 0) + l'min(dy, 0) of the projected dy
         const double lo = lo03(evr), hi = hi03(evr);
-        const double d = proj(DY[r], lo, hi), d4 = proj(DY4[r], L4[r], U4[r]);
+        const double d = osqp::polar_project(DY[r], lo, hi), d4 = osqp::polar_project(DY4[r], L4[r], U4[r]);
         dyp[r] = d;
         dyp4[r] = d4;
         if (kvr[r]) {
@@ -1041,8 +979,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
         double eps_abs = p.eps_abs, eps_rel = p.eps_rel, eps_pinf = p.eps_prim_inf, eps_dinf = p.eps_dual_inf;
         if (pri_res > OSQP_INF || dua_res > OSQP_INF) return MPCQP_STATUS_NON_CVX;
         if (approx) { eps_abs *= 10; eps_rel *= 10; eps_pinf *= 10; eps_dinf *= 10; }
-        const double eps_prim = eps_abs + eps_rel * mx[2];
-        const bool prim_ok = pri_res < eps_prim;
+        const bool prim_ok = pri_res < osqp::tolerance(eps_abs, eps_rel, mx[2]);
         bool prim_inf = false, dual_inf = false;
         if (!prim_ok && ndy > DIV_TOL && lh < eps_pinf * ndy) {
           double an = 0.0;
@@ -1054,8 +991,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
           an = wave_nmax(an);
           prim_inf = an < eps_pinf * ndy;
         }
-        const double eps_dual = eps_abs + eps_rel * (cinv * mx[6]);
-        const bool dual_ok = dua_res < eps_dual;
+        const bool dual_ok = dua_res < osqp::tolerance(eps_abs, eps_rel, cinv * mx[6]);
         if (!dual_ok && ndx > DIV_TOL && qd < cost_c * eps_dinf * ndx) {
           // is_dual_infeasible (P~ delta_x = P~x_new - P~x_old)
           double pd = 0.0, PDX[R];
@@ -1081,6 +1017,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
               const double v4 = (1.0 / e4c(r)) * (AK4[r] * dz);
               const double lo = lo03(evr), hi = hi03(evr);
               if (kvr[r]) {
+                // osqp::dual_ray_violates, written out (the call costs the Schur kernel 8 SGPR spills)
                 if ((hi < OSQP_INF * MIN_SCALING && v > eps_dinf * ndx) ||
                     (lo > -OSQP_INF * MIN_SCALING && v < -eps_dinf * ndx))
                   viol = 1.0;
@@ -1093,10 +1030,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
             dual_inf = viol == 0.0;
           }
         }
-        if (prim_ok && dual_ok) return approx ? MPCQP_STATUS_SOLVED_INACCURATE : MPCQP_STATUS_SOLVED;
-        if (prim_inf) return approx ? MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_PRIMAL_INFEASIBLE;
-        if (dual_inf) return approx ? MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE : MPCQP_STATUS_DUAL_INFEASIBLE;
-        return MPCQP_STATUS_UNSOLVED;
+        return osqp::termination_status(prim_ok, dual_ok, prim_inf, dual_inf, approx);
       };
       int st = MPCQP_STATUS_UNSOLVED;
       bool done = false, refactor = false;
@@ -1107,12 +1041,9 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
           done = st != MPCQP_STATUS_UNSOLVED;
         }
         if (pass == 1 || done || !is_adapt) continue;
-        const double pr_n = mx[1] / (mx[3] + DIV_TOL);
-        const double du_n = mx[5] / (mx[7] + DIV_TOL);
-        double est = rho * sqrt(pr_n / (du_n + DIV_TOL));
-        est = dmin(dmax(est, RHO_MIN), RHO_MAX);
-        if (est > rho * p.adaptive_rho_tolerance || est < rho / p.adaptive_rho_tolerance) {
-          rho = dmin(dmax(est, RHO_MIN), RHO_MAX);
+        const double est = osqp::rho_estimate(rho, mx[1], mx[3], mx[5], mx[7]);
+        if (osqp::rho_moved(est, rho, p.adaptive_rho_tolerance)) {
+          rho = dmin(dmax(est, RHO_MIN), RHO_MAX);  // (adapt_rho clamps the clamped estimate again)
           rho_updates += 1;
           refactor = !last;
         }
@@ -1199,10 +1130,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
     }
   }
   // ---- 6. store_solution + unscale + compute_grf extraction (A1RobotControl.cpp:555-561) --------
-  const bool has_sol = status != MPCQP_STATUS_PRIMAL_INFEASIBLE &&
-                       status != MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE &&
-                       status != MPCQP_STATUS_DUAL_INFEASIBLE &&
-                       status != MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE && status != MPCQP_STATUS_NON_CVX;
+  const bool has_sol = osqp::has_solution(status);
   const double ob = obj_sum;
   double xs0 = 0.0;
 #pragma unroll
@@ -1233,18 +1161,14 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
     int legs = 0;
     for (int l = 0; l < 4; ++l) legs |= ((nanmask >> (4 * l)) & 1ull) ? (1 << l) : 0;
     res->nan_legs = legs;
+    // osqp::objective_of(status, ob, cinv), written out on has_sol above (the call changes the
+    // kernel's instruction selection)
     double obj;
     if (has_sol) obj = ob * cinv;
     else if (status == MPCQP_STATUS_PRIMAL_INFEASIBLE || status == MPCQP_STATUS_PRIMAL_INFEASIBLE_INACCURATE) obj = OSQP_INF;
     else if (status == MPCQP_STATUS_DUAL_INFEASIBLE || status == MPCQP_STATUS_DUAL_INFEASIBLE_INACCURATE) obj = -OSQP_INF;
     else obj = NAN;
-    res->obj_val = obj;
-    res->pri_res = pri_res;
-    res->dua_res = dua_res;
-    res->rho = rho;
-    res->status = status;
-    res->iters = iters;
-    res->rho_updates = rho_updates;
+    osqp::store_info(res, obj, pri_res, dua_res, rho, status, iters, rho_updates);
   }
   return order_cost(iters, rho_updates);
 }

@@ -333,13 +333,10 @@ __device__ __forceinline__ void ld12(double (&c)[12], const double* p) {  // 12 
     c[2 * i + 1] = v.y;
   }
 }
-__device__ __forceinline__ void ld12s(double (&c)[12], const double* p) {  // a column of a stored factor
-#pragma unroll
-  for (int i = 0; i < 12; ++i) c[i] = p[mo(i)];
-}
-// The same column as 12 separate ds_read_b64, issued without waiting: the compiler pairs ld12s's
-// loads into ds_read2_b64, which moves 16 B per lane in 8 LDS-array cycles against 2 x 2 for two
-// ds_read_b64.  The compiler does not track these loads: the values are valid only after
+// A column of a stored factor (c[i] = p[mo(i)]) as 12 separate ds_read_b64, issued without waiting:
+// the compiler pairs plain loads of it into ds_read2_b64, which moves 16 B per lane in 8 LDS-array
+// cycles against 2 x 2 for two ds_read_b64.  The compiler does not track these loads: the values are
+// valid only after
 // lds_wait<n>(c), n = the number of LDS instructions issued after them that may stay in flight
 // (LDS returns in order; lgkmcnt holds at most 15).
 __device__ __forceinline__ unsigned lds_off(const double* p) {

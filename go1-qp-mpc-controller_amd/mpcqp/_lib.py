@@ -11,9 +11,9 @@ import os
 import numpy as np
 
 PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# MPCQP_LIB overrides the in-tree library (A/B kernel experiments only).
+# MPCQP_LIB / MPCQP_DEBUG_LIB override the in-tree libraries (A/B kernel experiments only).
 LIB_PATH = os.environ.get("MPCQP_LIB") or os.path.join(PKG_ROOT, "lib", "libmpcqp.so")
-DEBUG_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libmpcqp_debug.so")
+DEBUG_LIB_PATH = os.environ.get("MPCQP_DEBUG_LIB") or os.path.join(PKG_ROOT, "lib", "libmpcqp_debug.so")
 
 STATE_DIM, NUM_LEG, NUM_DOF, CONSTRAINT_DIM = 13, 4, 12, 20
 MAX_HORIZON = 20
