@@ -603,7 +603,6 @@ __device__ __forceinline__ void schur_gj_valu(double (&S)[64], SchurLds<N>& F, i
 template <int N, int R, class SM, class Mark>
 __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp_params& p, const Adisc& A, double cost_c,
                              double dtm, double (&RI)[R][3], Mark&& mark, double& smax) {
-  constexpr int QS = SchurCfg<N>::QS;
   constexpr int NI = SchurCfg<N>::NI;
   auto& sc = F.s;
   // the lane id through an opaque copy: the per-lane masks derived from it (t == pivot, ...) are

@@ -1,6 +1,7 @@
 // mpcqp_wave.hip — one WAVEFRONT per robot: the OSQP 0.6 solve of ConvexMpc's QP with the KKT
 // system solved through the problem's state-space (LQR) structure, all of it inside one 64-lane
-// wave, so that several robots share a CU (the dense path runs one 5-wave workgroup per CU).
+// wave, so that several robots share a CU (the dense path, mpcqp_kernels.hip, runs one workgroup of
+// 16 lanes per foot step per robot: 10 waves at N = 10).
 //
 // Reference path: A1RobotControl::compute_grf (src/a1_cpp/src/A1RobotControl.cpp:446-562) ->
 // ConvexMpc (src/a1_cpp/src/ConvexMpc.cpp:7-245) -> OsqpEigen 0.6.3 / OSQP 0.6 (restated in
@@ -34,9 +35,29 @@
 // projection) is a quad-perm DPP.  No barrier exists anywhere: the workgroup is the wave.
 // Arithmetic is binary64 throughout.
 #include "mpcqp_schur.h"
+#include "mpcqp_wave_riccati.h"
 
 namespace mpcqp {
 namespace wv {
+
+// The LDS image of one robot: the B_w rows, and the setup image recycled as the KKT form's factors.
+template <int N, int KS>
+struct WSmem {
+  using C = Cfg<N>;
+  static constexpr bool SACL = N <= ACL_MAXN;
+  alignas(16) double Bw[N][3][ND];  // rows 6-8 of B_d(k) = I_w^-1 skew(foot) dt (rows 9-11: dt/m I)
+  union U {
+    struct Hs {  // setup: record, Ruiz vectors
+      double rec[C::REC];
+      double D[C::n], Dt[C::n], q[C::n], E[C::m];
+      double lam[N][ND];  // gradient adjoint lambda_k (states 0..11)
+      double vec[2][16];  // sequential 13-vectors (gradient forward sweep)
+      double qn[C::n];     // this tick's gradient (warm start: q of the Ruiz passes is the old one)
+    } h;
+    // KS = 0: the Riccati factors; KS = 1: the impulse-space Schur form (mpcqp_schur.h)
+    typename std::conditional<KS == 0, RicFactors<N, SACL>, SchurLds<N>>::type f;
+  } u;
+};
 
 // Phase timing (debug builds with -DMPCQP_PHASE_TIMING): lane 0 of each traced robot appends
 // {phase id, s_memtime, s_memrealtime (100 MHz), 0} to the trace buffer instead of check records.
@@ -112,6 +133,12 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
   const double alpha = p.alpha, sigma = p.sigma;
   int nmark = 0;
   (void)nmark;
+  // the phase marks of code that lives in the two forms' headers
+  auto mark = [&](int id, long long cyc = -1) __attribute__((always_inline)) {
+    WV_MARK_AT(id, cyc);
+    (void)id;
+    (void)cyc;
+  };
   WV_MARK(0);
 
   // ---- 0. record -> LDS, non-finite guard -------------------------------------------------------
@@ -505,13 +532,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
       if constexpr (KS == 0) factorize_mfma<N>(sm, p, A, cost_c, dtm, Q2J);
       else {
         double smax;
-        schur_factor<N, R>(sm, F, p, A, cost_c, dtm, SRI,
-                           [&](int id, long long cyc = -1) __attribute__((always_inline)) {
-                             WV_MARK_AT(id, cyc);
-                             (void)id;
-                             (void)cyc;
-                           },
-                           smax);
+        schur_factor<N, R>(sm, F, p, A, cost_c, dtm, SRI, mark, smax);
         // The push-through identity subtracts B'(I - S^-1)B w from R'^-1 w: with S ill-conditioned
         // (large state weights, four feet in contact) the difference loses digits the Riccati form
         // keeps.  Such a robot leaves the loop at the next need_info iteration (one follows every
@@ -530,264 +551,143 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
     double U[R];
     double amp = 1.0;  // the Schur form's cancellation at the update_info iteration (schur_solve)
     auto kkt = [&](auto INFO) __attribute__((always_inline)) {
-    const bool tm_it = iter == 60;
-    if (tm_it) WV_MARK(40);
-    if constexpr (KS == 1) {
-      double W[R];
+      const bool tm_it = iter == 60;
+      if (tm_it) WV_MARK(40);
+      if constexpr (KS == 1) {
+        double W[R];
 #pragma unroll
-      for (int r = 0; r < R; ++r) W[r] = DI[r] * RHS[r];
-      schur_solve<N, R, decltype(INFO)::value>(F, W, SRI, vvr, U, amp);
-    } else if constexpr (NOACL) {
-      // Riccati form without Acl (sigma_k = -s_k):
-      //   backward  t_k = w_k - B_k' sigma_{k+1},  sigma_k = K_k' t_k + A' sigma_{k+1}  (sigma_N = 0)
-      //   parallel  g_k = G_k^-1 t_k
-      //   forward   u_k = g_k - K_k x_k,  x_{k+1} = A x_k + B_k u_k                    (x_0 = 0)
-      // (the same recursion: s_k = Acl_k' s_{k+1} - K_k' w_k, x_{k+1} = Acl_k x_k + B_k g_k)
-      double W[R], TT[R], G[R];
-      int kc[R], kk[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        W[r] = DI[r] * RHS[r];
-        TT[r] = 0.0;
-        U[r] = 0.0;
-        kc[r] = min(4 * r + ig, N - 1);
-        kk[r] = max(kc[r] - 1, 0);  // slot of K_k (k >= 1)
-      }
-      if (tm_it) WV_MARK(41);
-      {  // backward chain; a round's K_k columns (rows of K_k') serve its four steps, one per row
-        double kn[12], kcur[12], bcur[6];
-        ldcol(kn, &F.K[kk[(N - 1) >> 2]][idx]);
-        double cur = 0.0;
-        sfor<0, N>([&](auto J) {
-          constexpr int k = N - 1 - decltype(J)::value;
-          constexpr int r = k >> 2;
-          if constexpr (k == N - 1 || (k & 3) == 3) {  // entering round r (descending)
-            lds_wait<0>(kn);
-#pragma unroll
-            for (int e = 0; e < 12; ++e) kcur[e] = kn[e];
-            if constexpr (r >= 1) ldcol(kn, &F.K[kk[r - 1]][idx]);
-            bcur[0] = -sm.Bw[kc[r]][0][idx];
-            bcur[1] = -sm.Bw[kc[r]][1][idx];
-            bcur[2] = -sm.Bw[kc[r]][2][idx];
-            bcur[3] = a == 0 ? -dtm : 0.0;
-            bcur[4] = a == 1 ? -dtm : 0.0;
-            bcur[5] = a == 2 ? -dtm : 0.0;
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (k >= 1 && k < N - 1) {  // a middle step: one block (chain_bwd)
-            const double m = rmove2<row_of(k + 1), row_of(k)>(cur);
-            double tk = W[r], sn = m;
-            chain_bwd(m, bcur, CAT, kcur, tk, sn);
-            TT[r] = (q == row_of(k)) ? tk : TT[r];
-            cur = sn;
-            return;
-          }
-          double m = 0.0, tk = W[r];
-          if constexpr (k < N - 1) {
-            m = rmove2<row_of(k + 1), row_of(k)>(cur);
-            tk = mv6a(m, bcur, W[r]);
-          }
-          TT[r] = (q == row_of(k)) ? tk : TT[r];
-          if constexpr (k >= 1) {
-            const double as = k < N - 1 ? mv6lo_a(m, CAT, m) : 0.0;
-            cur = mv12a(tk, kcur, as);
-          }
-        });
-      }
-      if (tm_it) WV_MARK(42);
-      // g_k = G_k^-1 t_k: row idx of the packed upper triangle, element c at (min, max) of (idx, c);
-      // per-lane LDS addresses (constant) plus the round's compile-time offset
-      {
-        using lds_d = __attribute__((address_space(3))) const double;
-        double c0[12], c1[12];
-        auto ldg = [&](int r, double (&c)[12]) __attribute__((always_inline)) {
-#pragma unroll
-          for (int e = 0; e < 12; ++e)
-            c[e] = *(lds_d*)(GADR[e] + (unsigned)(sizeof(double) * GPS * 4 * r));
-        };
-        ldg(0, c0);
-        sfor<0, R>([&](auto RR) {
-          constexpr int r = decltype(RR)::value;
-          if constexpr (r + 1 < R) ldg(r + 1, (r & 1) ? c0 : c1);
-          G[r] = mv12(TT[r], (r & 1) ? c1 : c0);
-        });
-      }
-      if (tm_it) WV_MARK(43);
-      {  // forward chain; a round's K_k rows and B_w rows serve its four steps
-        double kn[12], kcur[12], bn[12], bcu[12];
-        ld12(kn, &F.K[kk[0]][mo(idx)]);
-        ld12(bn, &sm.Bw[kc[0]][av ? a : 2][0]);
-        double cur = 0.0;
-        sfor<0, N>([&](auto K) {
-          constexpr int k = decltype(K)::value;
-          constexpr int r = k >> 2;
-          if constexpr ((k & 3) == 0) {  // entering round r (ascending)
-#pragma unroll
-            for (int e = 0; e < 12; ++e) {
-              kcur[e] = kn[e];
-              bcu[e] = bn[e];
-            }
-            if constexpr (r + 1 < R) {
-              ld12(kn, &F.K[kk[r + 1]][mo(idx)]);
-              ld12(bn, &sm.Bw[kc[r + 1]][av ? a : 2][0]);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if constexpr (k >= 1 && k <= N - 2) {  // a middle step: one block (chain_fwd)
-            const double m = rmove2<row_of(k - 1), row_of(k)>(cur);
-            double nu = -G[r], ax = m, hb = 0.0;
-            chain_fwd(m, kcur, CAX, bcu, nu, ax, hb);
-            U[r] = (q == row_of(k)) ? -nu : U[r];
-            const double ls = dtm * legsum(nu);
-            const double bnu = leg == 2 ? hb : (leg == 3 ? ls : 0.0);
-            cur = ax - bnu;
-            return;
-          }
-          double m = 0.0, nu = -G[r];  // nu = -u_k = K_k x_k - g_k
-          if constexpr (k >= 1) {
-            m = rmove2<row_of(k - 1), row_of(k)>(cur);
-            nu = mv12a(m, kcur, -G[r]);
-          }
-          U[r] = (q == row_of(k)) ? -nu : U[r];
-          if constexpr (k <= N - 2) {
-            // B_k nu: rows 6-8 (leg-2 lanes) B_w nu, rows 9-11 (leg-3 lanes) dt/m times the legs' sum
-            const double hb = mv12(nu, bcu);
-            const double ls = dtm * legsum(nu);
-            const double bnu = leg == 2 ? hb : (leg == 3 ? ls : 0.0);
-            const double ax = k >= 1 ? mv6a(m, CAX, m) : 0.0;  // A x_k
-            cur = ax - bnu;
-          }
-        });
-      }
-      if (tm_it) WV_MARK(44);
-    } else {
-      // LDS operands are loaded one phase ahead of their use; sched_barrier keeps the scheduler from
-      // sinking a prefetch back down to its consumer (counted lgkmcnt waits then cover only it).
-      double W[R], AKw[R], SMv[R], G[R], Hh[R], XS[R], tt[R];
-      // Every phase's rows of all rounds are loaded one phase ahead (48 R VGPRs): Acl is stored only
-      // up to ACL_MAXN steps, three rounds.
-      static_assert(R <= 3, "the stored-Acl solve holds every round's rows in registers");
-      double cA[R][12], cB[R][12], cw[R][3];
-      int kc[R], kk[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        W[r] = DI[r] * RHS[r];
-        SMv[r] = 0.0;
-        XS[r] = 0.0;
-        kc[r] = min(4 * r + ig, N - 1);
-        kk[r] = max(kc[r] - 1, 0);  // slot of K_k (k >= 1)
-      }
-      double cn[12];
-#pragma unroll
-      for (int r = 0; r < R; ++r) ldcol(cA[r], &F.K[kk[r]][idx]);
-      // The chains load Acl one ROUND at a time: DPP row q takes the matrix of step 4 rr + gray(q) of
-      // round rr, the step that row computes (every chain step runs in the row of its step), so one
-      // 12-double load per lane serves four chain steps.
-      constexpr int NA = WSmem<N, KS>::NA;
-      auto aslot = [&](int rr) __attribute__((always_inline)) { return min(max(4 * rr + ig - 1, 0), NA - 1); };
-      if constexpr (N >= 3) ldcol(cn, &F.Acl[aslot((N - 2) >> 2)][idx]);
-      __builtin_amdgcn_sched_barrier(0);
-      // a_k = K_k' w_k (k >= 1)
-#pragma unroll
-      for (int r = 0; r < R; ++r) lds_wait<N >= 3 ? 12 : 0>(cA[r]);
-      mv_rounds<R>(W, cA, AKw);
-      __builtin_amdgcn_sched_barrier(0);
-      if (tm_it) WV_MARK(41);
-      // g_k's G_k^-1 rows and B_k' columns: issued when the backward chain enters its last round
-      // (three steps before their use), so they do not hold registers through the whole chain
-      auto load_g = [&]() __attribute__((always_inline)) {
+        for (int r = 0; r < R; ++r) W[r] = DI[r] * RHS[r];
+        schur_solve<N, R, decltype(INFO)::value>(F, W, SRI, vvr, U, amp);
+      } else if constexpr (NOACL) {
+        riccati_solve_noacl<N, R>(sm, F, DI, RHS, CAT, CAX, GADR, dtm, ig, q, leg, a, idx, tm_it, mark, U);
+      } else {
+        // LDS operands are loaded one phase ahead of their use; sched_barrier keeps the scheduler from
+        // sinking a prefetch back down to its consumer (counted lgkmcnt waits then cover only it).
+        double W[R], AKw[R], SMv[R], G[R], Hh[R], XS[R], tt[R];
+        // Every phase's rows of all rounds are loaded one phase ahead (48 R VGPRs): Acl is stored only
+        // up to ACL_MAXN steps, three rounds.
+        static_assert(R <= 3, "the stored-Acl solve holds every round's rows in registers");
+        double cA[R][12], cB[R][12], cw[R][3];
+        int kc[R], kk[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-          ld12(cB[r], &F.Gi[kc[r]][mo(idx)]);
-          cw[r][0] = sm.Bw[kc[r]][0][idx];
-          cw[r][1] = sm.Bw[kc[r]][1][idx];
-          cw[r][2] = sm.Bw[kc[r]][2][idx];
+          W[r] = DI[r] * RHS[r];
+          SMv[r] = 0.0;
+          XS[r] = 0.0;
+          kc[r] = min(4 * r + ig, N - 1);
+          kk[r] = max(kc[r] - 1, 0);  // slot of K_k (k >= 1)
         }
-      };
-      constexpr int KG = N - 2 >= 2 ? 2 : N - 2;  // the backward chain's step that issues them
-      if constexpr (KG < 1) load_g();
-      {  // backward chain: s_{N-1} = -a_{N-1}; s_k = Acl_k' s_{k+1} - a_k; SMv (row of k) = s_{k+1}
-        double cur = -AKw[(N - 1) >> 2];
-        double cc[12];
-        sfor<0, N - 1>([&](auto J) {
-          constexpr int k = N - 2 - decltype(J)::value;
-          const double mvv = rmove2<row_of(k + 1), row_of(k)>(cur);
-          SMv[k >> 2] = (q == row_of(k)) ? mvv : SMv[k >> 2];
-          if constexpr (k >= 1) {
-            if constexpr (k == N - 2 || (k & 3) == 3) {  // entering round k >> 2 (descending)
-              lds_wait<0>(cn);
+        double cn[12];
 #pragma unroll
-              for (int e = 0; e < 12; ++e) cc[e] = cn[e];
-              if constexpr (k >= 4) ldcol(cn, &F.Acl[aslot((k >> 2) - 1)][idx]);  // the next round's columns
-            }
-            if constexpr (k == KG) load_g();
-            __builtin_amdgcn_sched_barrier(0);
-            cur = mv12a(mvv, cc, -AKw[k >> 2]);
+        for (int r = 0; r < R; ++r) ldcol(cA[r], &F.K[kk[r]][idx]);
+        // The chains load Acl one ROUND at a time: DPP row q takes the matrix of step 4 rr + gray(q) of
+        // round rr, the step that row computes (every chain step runs in the row of its step), so one
+        // 12-double load per lane serves four chain steps.
+        constexpr int NA = RicFactors<N, true>::NA;
+        auto aslot = [&](int rr) __attribute__((always_inline)) { return min(max(4 * rr + ig - 1, 0), NA - 1); };
+        if constexpr (N >= 3) ldcol(cn, &F.Acl[aslot((N - 2) >> 2)][idx]);
+        __builtin_amdgcn_sched_barrier(0);
+        // a_k = K_k' w_k (k >= 1)
+#pragma unroll
+        for (int r = 0; r < R; ++r) lds_wait<N >= 3 ? 12 : 0>(cA[r]);
+        mv_rounds<R>(W, cA, AKw);
+        __builtin_amdgcn_sched_barrier(0);
+        if (tm_it) WV_MARK(41);
+        // g_k's G_k^-1 rows and B_k' columns: issued when the backward chain enters its last round
+        // (three steps before their use), so they do not hold registers through the whole chain
+        auto load_g = [&]() __attribute__((always_inline)) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            ld12(cB[r], &F.Gi[kc[r]][mo(idx)]);
+            cw[r][0] = sm.Bw[kc[r]][0][idx];
+            cw[r][1] = sm.Bw[kc[r]][1][idx];
+            cw[r][2] = sm.Bw[kc[r]][2][idx];
           }
-        });
-      }
-      if (tm_it) WV_MARK(42);
-      // g_k = G_k^-1 (w_k + B_k' s_{k+1})
-      auto ttr = [&](int r, double c0, double c1, double c2) __attribute__((always_inline)) {
-        const double c6[6] = {c0, c1, c2, a == 0 ? dtm : 0.0, a == 1 ? dtm : 0.0, a == 2 ? dtm : 0.0};
-        return W[r] + mv6(SMv[r], c6);
-      };
-      // h_k = B_k g_k: rows 6-8 (leg-2 lanes) B_w g, rows 9-11 (leg-3 lanes) dt/m times the sum of
-      // the legs' matching force component, rows 0-5 zero
-      auto hhr = [&](int r, double hb) __attribute__((always_inline)) {
-        const double ls = dtm * legsum(G[r]);
-        return leg == 2 ? hb : (leg == 3 ? ls : 0.0);
-      };
+        };
+        constexpr int KG = N - 2 >= 2 ? 2 : N - 2;  // the backward chain's step that issues them
+        if constexpr (KG < 1) load_g();
+        {  // backward chain: s_{N-1} = -a_{N-1}; s_k = Acl_k' s_{k+1} - a_k; SMv (row of k) = s_{k+1}
+          double cur = -AKw[(N - 1) >> 2];
+          double cc[12];
+          sfor<0, N - 1>([&](auto J) {
+            constexpr int k = N - 2 - decltype(J)::value;
+            const double mvv = rmove2<row_of(k + 1), row_of(k)>(cur);
+            SMv[k >> 2] = (q == row_of(k)) ? mvv : SMv[k >> 2];
+            if constexpr (k >= 1) {
+              if constexpr (k == N - 2 || (k & 3) == 3) {  // entering round k >> 2 (descending)
+                lds_wait<0>(cn);
 #pragma unroll
-      for (int r = 0; r < R; ++r) tt[r] = ttr(r, cw[r][0], cw[r][1], cw[r][2]);
-#pragma unroll
-      for (int r = 0; r < R; ++r) ld12(cA[r], &sm.Bw[kc[r]][av ? a : 2][0]);  // for h_k
-      __builtin_amdgcn_sched_barrier(0);
-      mv_rounds<R>(tt, cB, G);
-      if constexpr (N >= 3) ld12(cn, &F.Acl[aslot(0)][mo(idx)]);
-      __builtin_amdgcn_sched_barrier(0);
-      {
-        double hb[R];
-        mv_rounds<R>(G, cA, hb);
-#pragma unroll
-        for (int r = 0; r < R; ++r) Hh[r] = hhr(r, hb[r]);
-      }
-      if (tm_it) WV_MARK(43);
-      // u_k's K_k rows: issued three steps before the forward chain ends
-      auto load_u = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) ld12(cB[r], &F.K[kk[r]][mo(idx)]);
-      };
-      constexpr int KU = N - 2 >= 1 ? (N - 3 > 1 ? N - 3 : 1) : 0;  // two steps before the end
-      if constexpr (KU < 1) load_u();
-      {  // forward chain: x_1 = h_0; x_{k+1} = Acl_k x_k + h_k; XS (row of k) = x_k
-        double cur = Hh[0];
-        double cc[12];
-        sfor<1, N>([&](auto K) {
-          constexpr int k = decltype(K)::value;
-          const double mvv = rmove2<row_of(k - 1), row_of(k)>(cur);
-          XS[k >> 2] = (q == row_of(k)) ? mvv : XS[k >> 2];
-          if constexpr (k <= N - 2) {
-            if constexpr (k == 1 || (k & 3) == 0) {  // entering round k >> 2 (ascending)
-#pragma unroll
-              for (int e = 0; e < 12; ++e) cc[e] = cn[e];
-              if constexpr (4 * ((k >> 2) + 1) <= N - 2) ld12(cn, &F.Acl[aslot((k >> 2) + 1)][mo(idx)]);
+                for (int e = 0; e < 12; ++e) cc[e] = cn[e];
+                if constexpr (k >= 4) ldcol(cn, &F.Acl[aslot((k >> 2) - 1)][idx]);  // the next round's columns
+              }
+              if constexpr (k == KG) load_g();
+              __builtin_amdgcn_sched_barrier(0);
+              cur = mv12a(mvv, cc, -AKw[k >> 2]);
             }
-            if constexpr (k == KU) load_u();
-            __builtin_amdgcn_sched_barrier(0);
-            cur = mv12a(mvv, cc, Hh[k >> 2]);
-          }
-        });
-      }
-      if (tm_it) WV_MARK(44);
-      // u_k = g_k - K_k x_k (x_0 = 0)
-      double kx[R];
-      mv_rounds<R>(XS, cB, kx);
+          });
+        }
+        if (tm_it) WV_MARK(42);
+        // g_k = G_k^-1 (w_k + B_k' s_{k+1})
+        auto ttr = [&](int r, double c0, double c1, double c2) __attribute__((always_inline)) {
+          const double c6[6] = {c0, c1, c2, a == 0 ? dtm : 0.0, a == 1 ? dtm : 0.0, a == 2 ? dtm : 0.0};
+          return W[r] + mv6(SMv[r], c6);
+        };
+        // h_k = B_k g_k: rows 6-8 (leg-2 lanes) B_w g, rows 9-11 (leg-3 lanes) dt/m times the sum of
+        // the legs' matching force component, rows 0-5 zero
+        auto hhr = [&](int r, double hb) __attribute__((always_inline)) {
+          const double ls = dtm * legsum(G[r]);
+          return leg == 2 ? hb : (leg == 3 ? ls : 0.0);
+        };
 #pragma unroll
-      for (int r = 0; r < R; ++r) U[r] = G[r] - kx[r];
-    }
-    if (tm_it) WV_MARK(45);
-    };  // kkt
+        for (int r = 0; r < R; ++r) tt[r] = ttr(r, cw[r][0], cw[r][1], cw[r][2]);
+#pragma unroll
+        for (int r = 0; r < R; ++r) ld12(cA[r], &sm.Bw[kc[r]][av ? a : 2][0]);  // for h_k
+        __builtin_amdgcn_sched_barrier(0);
+        mv_rounds<R>(tt, cB, G);
+        if constexpr (N >= 3) ld12(cn, &F.Acl[aslot(0)][mo(idx)]);
+        __builtin_amdgcn_sched_barrier(0);
+        {
+          double hb[R];
+          mv_rounds<R>(G, cA, hb);
+#pragma unroll
+          for (int r = 0; r < R; ++r) Hh[r] = hhr(r, hb[r]);
+        }
+        if (tm_it) WV_MARK(43);
+        // u_k's K_k rows: issued three steps before the forward chain ends
+        auto load_u = [&]() __attribute__((always_inline)) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) ld12(cB[r], &F.K[kk[r]][mo(idx)]);
+        };
+        constexpr int KU = N - 2 >= 1 ? (N - 3 > 1 ? N - 3 : 1) : 0;  // two steps before the end
+        if constexpr (KU < 1) load_u();
+        {  // forward chain: x_1 = h_0; x_{k+1} = Acl_k x_k + h_k; XS (row of k) = x_k
+          double cur = Hh[0];
+          double cc[12];
+          sfor<1, N>([&](auto K) {
+            constexpr int k = decltype(K)::value;
+            const double mvv = rmove2<row_of(k - 1), row_of(k)>(cur);
+            XS[k >> 2] = (q == row_of(k)) ? mvv : XS[k >> 2];
+            if constexpr (k <= N - 2) {
+              if constexpr (k == 1 || (k & 3) == 0) {  // entering round k >> 2 (ascending)
+#pragma unroll
+                for (int e = 0; e < 12; ++e) cc[e] = cn[e];
+                if constexpr (4 * ((k >> 2) + 1) <= N - 2) ld12(cn, &F.Acl[aslot((k >> 2) + 1)][mo(idx)]);
+              }
+              if constexpr (k == KU) load_u();
+              __builtin_amdgcn_sched_barrier(0);
+              cur = mv12a(mvv, cc, Hh[k >> 2]);
+            }
+          });
+        }
+        if (tm_it) WV_MARK(44);
+        // u_k = g_k - K_k x_k (x_0 = 0)
+        double kx[R];
+        mv_rounds<R>(XS, cB, kx);
+#pragma unroll
+        for (int r = 0; r < R; ++r) U[r] = G[r] - kx[r];
+      }
+      if (tm_it) WV_MARK(45);
+    };
 
     // ---- update_x / update_z / update_y, and P~x by the KKT identity P~x~ = rhs - sigma x~ - A~'rho A~x~
     // this iteration's deltas, for the infeasibility tests of a need_info iteration only
@@ -796,53 +696,53 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
       constexpr bool info = decltype(INFO)::value;
       double xt[R], xz[R], zt[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      xt[r] = DI[r] * U[r];
-      const double xp = dpp<QP_PRIM>(xt[r]);
-      xz[r] = dpp<QP_B2>(xt[r]);
-      zt[r] = AK0[r] * xp + AK1[r] * xz[r];
-      {  // (fmin/fmax = the reference's c_min/c_max on these non-NaN operands)
-        const double zr = alpha * zt[r] + (1.0 - alpha) * Z[r];
-        const double zn = fmin(fmax(zr + rinv * Y[r], LO03), HI03);
-        const double dyv = rho * (zr - zn);
-        Z[r] = zn;
-        Y[r] = Y[r] + dyv;
-        if constexpr (info) DY[r] = dyv;
+      for (int r = 0; r < R; ++r) {
+        xt[r] = DI[r] * U[r];
+        const double xp = dpp<QP_PRIM>(xt[r]);
+        xz[r] = dpp<QP_B2>(xt[r]);
+        zt[r] = AK0[r] * xp + AK1[r] * xz[r];
+        {  // (fmin/fmax = the reference's c_min/c_max on these non-NaN operands)
+          const double zr = alpha * zt[r] + (1.0 - alpha) * Z[r];
+          const double zn = fmin(fmax(zr + rinv * Y[r], LO03), HI03);
+          const double dyv = rho * (zr - zn);
+          Z[r] = zn;
+          Y[r] = Y[r] + dyv;
+          if constexpr (info) DY[r] = dyv;
+        }
       }
-    }
       // row 4, packed: lane a projects round 4 pr + a
       double V4P[NP], T4P[NP];
 #pragma unroll
-    for (int pr = 0; pr < NP; ++pr) {
-      const double zt4 = AK4P[pr] * pack_of([&](int r) { return xz[r]; }, pr);
-      const double r4 = RHO4P[pr];
-      const double zr = alpha * zt4 + (1.0 - alpha) * Z4P[pr];
-      const double zn = fmin(fmax(zr + RI4P[pr] * Y4P[pr], L4P[pr]), U4P[pr]);
-      const double dyv = r4 * (zr - zn);
-      Z4P[pr] = zn;
-      Y4P[pr] = Y4P[pr] + dyv;
-      if constexpr (info) DY4P[pr] = dyv;
-      V4P[pr] = RHO4P[pr] * Z4P[pr] - Y4P[pr];
-      T4P[pr] = KS == 0 ? RHO4P[pr] * zt4 : 0.0;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      // every lane updates (values of padding lanes / steps past N are never read unmasked)
-      const double xo = X[r];
-      const double xn = alpha * xt[r] + (1.0 - alpha) * xo;
-      if constexpr (info) DX[r] = xn - xo;
-      X[r] = xn;
-      const double ak4 = unpack(AK4P, r);
-      if constexpr (KS == 0) {  // the Riccati variant carries P~x; the Schur form computes it at checks
-        const double kd = quad_at(rho * zt[r], unpack(T4P, r), AK0[r], AK1[r], ak4, a);
-        const double pxt = (RHS[r] - sigma * xt[r]) - kd;
-        if constexpr (info) PXO[r] = PX[r];
-        PX[r] = alpha * pxt + (1.0 - alpha) * PX[r];
+      for (int pr = 0; pr < NP; ++pr) {
+        const double zt4 = AK4P[pr] * pack_of([&](int r) { return xz[r]; }, pr);
+        const double r4 = RHO4P[pr];
+        const double zr = alpha * zt4 + (1.0 - alpha) * Z4P[pr];
+        const double zn = fmin(fmax(zr + RI4P[pr] * Y4P[pr], L4P[pr]), U4P[pr]);
+        const double dyv = r4 * (zr - zn);
+        Z4P[pr] = zn;
+        Y4P[pr] = Y4P[pr] + dyv;
+        if constexpr (info) DY4P[pr] = dyv;
+        V4P[pr] = RHO4P[pr] * Z4P[pr] - Y4P[pr];
+        T4P[pr] = KS == 0 ? RHO4P[pr] * zt4 : 0.0;
       }
-      // next right-hand side sigma x - q~ + A~'(rho z - y) (recomputed below when adapt_rho changes rho)
-      const double at = quad_at(rho * Z[r] - Y[r], unpack(V4P, r), AK0[r], AK1[r], ak4, a);
-      RHS[r] = (sigma * X[r] - Qv[r]) + at;
-    }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        // every lane updates (values of padding lanes / steps past N are never read unmasked)
+        const double xo = X[r];
+        const double xn = alpha * xt[r] + (1.0 - alpha) * xo;
+        if constexpr (info) DX[r] = xn - xo;
+        X[r] = xn;
+        const double ak4 = unpack(AK4P, r);
+        if constexpr (KS == 0) {  // the Riccati variant carries P~x; the Schur form computes it at checks
+          const double kd = quad_at(rho * zt[r], unpack(T4P, r), AK0[r], AK1[r], ak4, a);
+          const double pxt = (RHS[r] - sigma * xt[r]) - kd;
+          if constexpr (info) PXO[r] = PX[r];
+          PX[r] = alpha * pxt + (1.0 - alpha) * PX[r];
+        }
+        // next right-hand side sigma x - q~ + A~'(rho z - y) (recomputed below when adapt_rho changes rho)
+        const double at = quad_at(rho * Z[r] - Y[r], unpack(V4P, r), AK0[r], AK1[r], ak4, a);
+        RHS[r] = (sigma * X[r] - Qv[r]) + at;
+      }
     };
 
     // The iterations before the next one that needs update_info (a termination check, an adapt_rho

@@ -4,7 +4,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -I go1-qp-mpc-controller_amd/csrc tools/mb/mb_gj.hip -o tools/mb/mb_gj
 #include <hip/hip_runtime.h>
 #include <stdio.h>
-#include "mpcqp_wave_common.h"
+#include "mpcqp_wave_riccati.h"
 using namespace mpcqp::wv;
 
 __global__ __launch_bounds__(64) void gj_kernel(double* out, long long* cyc, int iters) {
