@@ -101,6 +101,63 @@ hipError_t launch_assemble(int horizon, const double* states, int batch, double*
 }
 
 namespace as {
+// Balance record (MPCQP_BAL_*) from the raw state row, root_rot_mat_z of the plan input row, the gains and,
+// when a command slot is given, the kp_linear the command stage switches by position locking
+// (GazeboA1ROS.cpp:167-188; read by A1RobotControl.cpp:380).  Pure copies: bitwise mpcqp/balance.py
+// assemble_balance.
+__device__ __forceinline__ double balance_value(const mpcqp_balance_gains& g, const double* __restrict__ s,
+                                                const double* __restrict__ in, const double* __restrict__ cs, int k) {
+  if (k < MPCQP_BAL_POS_D) return s[MPCQP_ST_POS + k - MPCQP_BAL_POS];
+  if (k < MPCQP_BAL_ROT) return s[MPCQP_ST_POS_D + k - MPCQP_BAL_POS_D];
+  if (k < MPCQP_BAL_ROT_Z) return s[MPCQP_ST_ROT + k - MPCQP_BAL_ROT];
+  if (k < MPCQP_BAL_LIN_VEL) return in[MPCQP_PL_ROT_Z + k - MPCQP_BAL_ROT_Z];
+  if (k < MPCQP_BAL_LIN_VEL_D) return s[MPCQP_ST_LIN_VEL + k - MPCQP_BAL_LIN_VEL];
+  if (k < MPCQP_BAL_ANG_VEL) return s[MPCQP_ST_LIN_VEL_D + k - MPCQP_BAL_LIN_VEL_D];
+  if (k < MPCQP_BAL_ANG_VEL_D) return s[MPCQP_ST_ANG_VEL + k - MPCQP_BAL_ANG_VEL];
+  if (k < MPCQP_BAL_EULER) return s[MPCQP_ST_ANG_VEL_D + k - MPCQP_BAL_ANG_VEL_D];
+  if (k < MPCQP_BAL_EULER_D) return s[MPCQP_ST_EULER + k - MPCQP_BAL_EULER];
+  if (k < MPCQP_BAL_KP_LIN) return s[MPCQP_ST_EULER_D + k - MPCQP_BAL_EULER_D];
+  if (k < MPCQP_BAL_MASS) {  // the four gain triples; k - KP_LIN in 0 .. 11
+    const int e = k - MPCQP_BAL_KP_LIN, a = e % 3;
+    const double kp = a == 0 ? g.kp_linear[0] : (a == 1 ? g.kp_linear[1] : g.kp_linear[2]);
+    const double kd = a == 0 ? g.kd_linear[0] : (a == 1 ? g.kd_linear[1] : g.kd_linear[2]);
+    const double ap = a == 0 ? g.kp_angular[0] : (a == 1 ? g.kp_angular[1] : g.kp_angular[2]);
+    const double ad = a == 0 ? g.kd_angular[0] : (a == 1 ? g.kd_angular[1] : g.kd_angular[2]);
+    if (e < 3) return cs ? cs[MPCQP_CS_KP_LINEAR + a] : kp;
+    return e < 6 ? kd : (e < 9 ? ap : ad);
+  }
+  if (k == MPCQP_BAL_MASS) return s[MPCQP_ST_MASS];
+  if (k < MPCQP_BAL_CONTACTS) return s[MPCQP_ST_FEET + k - MPCQP_BAL_FEET];
+  if (k < MPCQP_BAL_CONTACTS + 4) return s[MPCQP_ST_CONTACTS + k - MPCQP_BAL_CONTACTS];
+  return 0.0;  // padding
+}
+
+// 64 lanes per robot as assemble_kernel: lane l writes doubles l and l + 64 of the 72, coalesced.
+__global__ void __launch_bounds__(256) assemble_balance_kernel(const mpcqp_balance_gains g,
+                                                               const double* __restrict__ states,
+                                                               const double* __restrict__ plan_in,
+                                                               const double* __restrict__ cmd_state, int batch,
+                                                               double* __restrict__ recs) {
+  const int b = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  const int lane = threadIdx.x & 63;
+  if (b >= batch) return;
+  const double* s = states + (size_t)MPCQP_ST_SIZE * b;
+  const double* in = plan_in + (size_t)MPCQP_PL_SIZE * b;
+  const double* cs = cmd_state ? cmd_state + (size_t)MPCQP_CS_SIZE * b : nullptr;
+  double* r = recs + (size_t)MPCQP_BAL_SIZE * b;
+  for (int k = lane; k < MPCQP_BAL_SIZE; k += 64) r[k] = balance_value(g, s, in, cs, k);
+}
+}  // namespace as
+
+hipError_t launch_assemble_balance(const mpcqp_balance_gains& g, const double* states, const double* plan_in,
+                                   const double* cmd_state, int batch, double* recs, void* stream) {
+  const long threads = 64L * batch;
+  hipLaunchKernelGGL(as::assemble_balance_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, g, states, plan_in, cmd_state, batch, recs);
+  return hipGetLastError();
+}
+
+namespace as {
 // Indexed slot copy: dst[dst_idx[i]] = src[src_idx[i]] (identity where an index array is null), one
 // 256-thread block per slot, coalesced along the slot.
 __global__ void __launch_bounds__(256) copy_slots_kernel(const double* __restrict__ src, const int* __restrict__ sidx,

@@ -473,9 +473,11 @@ __device__ __forceinline__ void scale(Ws& w, const mpcqp_params& p) {
 
 __global__ void __launch_bounds__(64) balance_kernel(const double* __restrict__ recs, int batch,
                                                      mpcqp_balance_params bp, mpcqp_params p,
-                                                     mpcqp_result* __restrict__ out) {
+                                                     mpcqp_result* __restrict__ out, const int* __restrict__ type,
+                                                     int want) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= batch) return;
+  if (type && type[b] != want) return;  // typed solve: the robot takes the other branch, nothing is written
   const double* rec = recs + (size_t)MPCQP_BAL_SIZE * b;
   mpcqp_result* res = out + b;
   bool finite = true;
@@ -619,9 +621,9 @@ __global__ void __launch_bounds__(64) balance_kernel(const double* __restrict__ 
 }  // namespace bal
 
 hipError_t launch_balance(const mpcqp_balance_params& bp, const mpcqp_params& p, const double* recs, int batch,
-                          mpcqp_result* out, void* stream) {
+                          const int* type, int want, mpcqp_result* out, void* stream) {
   hipLaunchKernelGGL(bal::balance_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, recs, batch, bp,
-                     p, out);
+                     p, out, type, want);
   return hipGetLastError();
 }
 

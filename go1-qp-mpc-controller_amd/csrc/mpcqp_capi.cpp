@@ -369,9 +369,11 @@ int32_t mpcqp_destroy(mpcqp_handle* h) {
 
 static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32_t batch,
                                  mpcqp_result* d_results, double* d_solution, double* d_trace,
-                                 int32_t trace_cap, void* stream, double* d_state = nullptr) {
+                                 int32_t trace_cap, void* stream, double* d_state = nullptr,
+                                 const int32_t* d_type = nullptr, int32_t type = 0) {
   if (!h || batch < 0 || (batch > 0 && (!d_records || !d_results))) return MPCQP_ERR_INVALID_ARG;
   if (d_state && effective_path(h) != 3) return MPCQP_ERR_INVALID_ARG;  // warm start: the wave path
+  if (d_type && effective_path(h) != 3) return MPCQP_ERR_INVALID_ARG;   // typed solve: the wave path
   if (batch == 0) return MPCQP_OK;
   DeviceGuard dg(h->device);
   hipError_t e = dg.err;
@@ -393,6 +395,8 @@ static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32
   a.stream = stream;
   a.p = h->p;
   a.hint = mpcqp::OrderHint{};  // input order (the cross-check paths ignore the hint)
+  a.type = d_type;
+  a.want = type;
   switch (effective_path(h)) {
 #ifdef MPCQP_DEBUG_PATHS
     case 1: e = mpcqp::launch_solve_any(a); break;
@@ -404,10 +408,15 @@ static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32
       const bool hint = order_hint_on(h, d_state != nullptr);
       h->last_batch = batch;
       h->last_parts = parts;
-      h->last_hint = hint;
+      h->last_hint = hint || d_type;
       // part i's order_kernel, ahead of its scale_kernel and wave_kernel on the part's stream
       auto order_part = [&](mpcqp::LaunchArgs& ai, int i, int b0) {
-        if (!hint) return hipSuccess;
+        if (!hint && !d_type) return hipSuccess;
+        if (!hint) {  // a typed solve still needs an order[]: the identity with holes, no stored state
+          ai.hint.order = h->ord_order + b0;
+          ai.hint.identity = true;
+          return mpcqp::launch_order(ai, mpcqp_handle::KMAX);
+        }
         ai.hint.order = h->ord_order + b0;
         ai.hint.key = h->ord_key + b0;
         ai.hint.contacts = h->ord_contacts + b0;
@@ -457,6 +466,7 @@ static int32_t solve_device_impl(mpcqp_handle* h, const double* d_records, int32
         ai.trace_cap = d_trace && trace_cap > b0 ? trace_cap - b0 : 0;
         ai.wstate = d_state ? d_state + ws * b0 : nullptr;
         ai.fallback = h->fb + 4 * i;
+        ai.type = d_type ? d_type + b0 : nullptr;
         if (i == 0) {
           ai.stream = stream;
           e = order_part(ai, i, b0);
@@ -498,6 +508,13 @@ int32_t mpcqp_solve_batch_warm_device(mpcqp_handle* h, const double* d_records, 
                                       mpcqp_result* d_results, double* d_solution, void* stream) {
   if (batch > 0 && !d_state) return MPCQP_ERR_INVALID_ARG;
   return solve_device_impl(h, d_records, batch, d_results, d_solution, nullptr, 0, stream, d_state);
+}
+
+int32_t mpcqp_solve_batch_warm_typed_device(mpcqp_handle* h, const double* d_records, int32_t batch, double* d_state,
+                                            const int32_t* d_type, int32_t type, mpcqp_result* d_results,
+                                            double* d_solution, void* stream) {
+  if (batch > 0 && !d_state) return MPCQP_ERR_INVALID_ARG;
+  return solve_device_impl(h, d_records, batch, d_results, d_solution, nullptr, 0, stream, d_state, d_type, type);
 }
 
 static int32_t solve_host_impl(mpcqp_handle* h, const double* h_records, int32_t batch, double* d_state,
@@ -614,14 +631,46 @@ void mpcqp_plan_default_params(mpcqp_plan_params* p) {
 
 int32_t mpcqp_plan_state_size(void) { return mpcqp::plan_state_doubles(); }
 
-int32_t mpcqp_leg_plan_device(const mpcqp_plan_params* pp, double dt, double* d_states, const double* d_plan_in,
-                              int32_t batch, double* d_plan_state, double* d_tq_records, double* d_plan_out,
-                              void* stream) {
+int32_t mpcqp_leg_plan_typed_device(const mpcqp_plan_params* pp, double dt, double* d_states,
+                                    const double* d_plan_in, int32_t batch, double* d_plan_state,
+                                    double* d_tq_records, double* d_plan_out, const int32_t* d_type, void* stream) {
   if (!pp || batch < 0 || !(dt > 0.0) || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
   if (batch > 0 && (!d_states || !d_plan_in || !d_plan_state)) return MPCQP_ERR_INVALID_ARG;
   if (batch == 0) return MPCQP_OK;
-  return mpcqp::launch_leg_plan(*pp, dt, d_states, d_plan_in, batch, d_plan_state, d_tq_records, d_plan_out, stream) ==
-                 hipSuccess
+  return mpcqp::launch_leg_plan(*pp, dt, d_states, d_plan_in, batch, d_plan_state, d_tq_records, d_plan_out, d_type,
+                                stream) == hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
+int32_t mpcqp_leg_plan_device(const mpcqp_plan_params* pp, double dt, double* d_states, const double* d_plan_in,
+                              int32_t batch, double* d_plan_state, double* d_tq_records, double* d_plan_out,
+                              void* stream) {
+  return mpcqp_leg_plan_typed_device(pp, dt, d_states, d_plan_in, batch, d_plan_state, d_tq_records, d_plan_out,
+                                     nullptr, stream);
+}
+
+void mpcqp_command_default_params(mpcqp_command_params* p) {
+  if (!p) return;
+  p->body_height_init = 0.2;     // GazeboA1ROS.h:133
+  p->body_height_max = 0.32;     // A1Params.h:16
+  p->body_height_min = 0.1;      // A1Params.h:17
+  p->vel_lock_threshold = 0.05;  // GazeboA1ROS.cpp:180
+  p->kp_linear[0] = 100.0;       // Go1CtrlStates.hpp:279-281
+  p->kp_linear[1] = 100.0;
+  p->kp_linear[2] = 300.0;
+  p->kp_linear_lock_x = 100.0;   // Go1CtrlStates.hpp:304-305
+  p->kp_linear_lock_y = 100.0;
+}
+
+int32_t mpcqp_command_state_size(void) { return MPCQP_CS_SIZE; }
+
+int32_t mpcqp_command_device(const mpcqp_command_params* cp, double dt, double* d_cmd, double* d_states,
+                             double* d_plan_in, int32_t batch, double* d_cmd_state, void* stream) {
+  if (!cp || batch < 0 || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_cmd || !d_states || !d_plan_in || !d_cmd_state)) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_command(*cp, dt, d_cmd, d_states, d_plan_in, batch, d_cmd_state, stream) == hipSuccess
              ? MPCQP_OK
              : MPCQP_ERR_HIP;
 }
@@ -682,16 +731,45 @@ void mpcqp_balance_default_params(mpcqp_balance_params* p) {
   p->f_max = 180.0;  // :14-15
 }
 
-int32_t mpcqp_balance_solve_device(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* d_records,
-                                   int32_t batch, mpcqp_result* d_results, void* stream) {
+int32_t mpcqp_balance_solve_typed_device(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* d_records,
+                                         int32_t batch, const int32_t* d_type, int32_t type, mpcqp_result* d_results,
+                                         void* stream) {
   if (!h || !bp || batch < 0 || (batch > 0 && (!d_records || !d_results))) return MPCQP_ERR_INVALID_ARG;
   if (batch == 0) return MPCQP_OK;
   DeviceGuard dg(h->device);
   hipError_t e = dg.err;
   if (e != hipSuccess) return set_hip_error(h, e, "hipSetDevice");
-  e = mpcqp::launch_balance(*bp, h->p, d_records, batch, d_results, stream);
+  e = mpcqp::launch_balance(*bp, h->p, d_records, batch, d_type, type, d_results, stream);
   if (e != hipSuccess) return set_hip_error(h, e, "balance_kernel launch");
   return MPCQP_OK;
+}
+
+int32_t mpcqp_balance_solve_device(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* d_records,
+                                   int32_t batch, mpcqp_result* d_results, void* stream) {
+  return mpcqp_balance_solve_typed_device(h, bp, d_records, batch, nullptr, 0, d_results, stream);
+}
+
+void mpcqp_balance_default_gains(mpcqp_balance_gains* g) {
+  if (!g) return;
+  const double kp[3] = {100.0, 100.0, 300.0}, kd[3] = {70.0, 70.0, 120.0};  // Go1CtrlStates.hpp:279-288
+  const double ap[3] = {150.0, 150.0, 1.0}, ad[3] = {4.5, 4.5, 30.0};       // :293-302
+  for (int i = 0; i < 3; ++i) {
+    g->kp_linear[i] = kp[i];
+    g->kd_linear[i] = kd[i];
+    g->kp_angular[i] = ap[i];
+    g->kd_angular[i] = ad[i];
+  }
+}
+
+int32_t mpcqp_assemble_balance_device(const mpcqp_balance_gains* gains, const double* d_states,
+                                      const double* d_plan_in, const double* d_cmd_state, int32_t batch,
+                                      double* d_bal_records, void* stream) {
+  if (!gains || batch < 0 || (batch > 0 && (!d_states || !d_plan_in || !d_bal_records))) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_assemble_balance(*gains, d_states, d_plan_in, d_cmd_state, batch, d_bal_records, stream) ==
+                 hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
 }
 
 int32_t mpcqp_balance_solve_host(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* h_records,
@@ -809,7 +887,8 @@ int32_t mpcqp_debug_launch_order(mpcqp_handle* h, int32_t* host_out, int32_t cap
   if (e != hipSuccess) return -set_hip_error(h, e, "mpcqp_debug_launch_order");
   // a part's order holds part-local indices
   for (int i = 0; i < h->last_parts; ++i)
-    for (int b = h->last_bnd[i]; b < h->last_bnd[i + 1] && b < nout; ++b) host_out[b] += h->last_bnd[i];
+    for (int b = h->last_bnd[i]; b < h->last_bnd[i + 1] && b < nout; ++b)
+      if (host_out[b] >= 0) host_out[b] += h->last_bnd[i];  // (-1: a place a typed solve left empty)
   return nout;
 }
 

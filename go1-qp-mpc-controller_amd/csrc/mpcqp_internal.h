@@ -34,6 +34,7 @@ struct OrderHint {
   int* contacts;  // [robots] contact mask (bit l = leg l) the robot was last solved with (order_kernel)
   int* layout;    // this part's ORDER_LAYOUT_INTS: the batch and part layout the state was written for
   int whole, parts, part, first;  // this call's layout: whole batch, parts, this part, its first robot
+  bool identity;  // a typed solve with the hint off: order[] = the identity with holes, no stored state used
 };
 
 // One (part of a) solve.  recs .. wstate and hint.order/key/contacts point at the part's first robot
@@ -53,6 +54,11 @@ struct LaunchArgs {
   void* stream;
   mpcqp_params p;
   OrderHint hint;  // wave path: launch order (hint.order == nullptr: input order)
+  // typed solve (mpcqp_solve_batch_warm_typed_device): robot b is solved iff !type || type[b] == want.
+  // order_kernel gives the others' places an index outside the batch, which wave_kernel skips, and
+  // scale_kernel leaves them alone; type points at the part's first robot.
+  const int* type;
+  int want;
 };
 
 // Formulation only (mpcqp_build.hip): ConvexMpc::calculate_qp_mats, horizons 1..20
@@ -106,7 +112,7 @@ hipError_t launch_copy_slots(const double* src, const int* sidx, double* dst, co
 
 // Upstream leg plan: gait, footholds, swing-leg PD force, contacts, terrain fit (mpcqp_legplan.hip)
 hipError_t launch_leg_plan(const mpcqp_plan_params& pp, double dt, double* states, const double* plan_in, int batch,
-                           double* slots, double* tq, double* out, void* stream);
+                           double* slots, double* tq, double* out, const int* type, void* stream);
 int plan_state_doubles();  // doubles per robot of the plan slot
 
 // State front end: frames, leg kinematics, Kalman estimator (mpcqp_estimate.hip)
@@ -116,6 +122,13 @@ int estimator_state_doubles();  // doubles per robot of the estimator slot
 
 // Single-step QP balance controller (mpcqp_balance.hip)
 hipError_t launch_balance(const mpcqp_balance_params& bp, const mpcqp_params& p, const double* recs, int batch,
-                          mpcqp_result* out, void* stream);
+                          const int* type, int want, mpcqp_result* out, void* stream);
+// Balance records from the raw robot state (mpcqp_assemble.hip)
+hipError_t launch_assemble_balance(const mpcqp_balance_gains& g, const double* states, const double* plan_in,
+                                   const double* cmd_state, int batch, double* recs, void* stream);
+
+// Command stage: the joystick command block of main_update (mpcqp_command.hip)
+hipError_t launch_command(const mpcqp_command_params& cp, double dt, double* cmds, double* states, double* plan_in,
+                          int batch, double* slots, void* stream);
 
 }  // namespace mpcqp

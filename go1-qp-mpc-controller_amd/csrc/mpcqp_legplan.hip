@@ -134,7 +134,8 @@ __device__ __forceinline__ void pinv3_apply(double a00, double a01, double a02, 
 __global__ __launch_bounds__(256) void plan_kernel(const mpcqp_plan_params pp, const double dt,
                                                    double* __restrict__ states, const double* __restrict__ plan_in,
                                                    const int batch, double* __restrict__ slots,
-                                                   double* __restrict__ tq, double* __restrict__ out) {
+                                                   double* __restrict__ tq, double* __restrict__ out,
+                                                   const int* __restrict__ type) {
 #pragma clang fp contract(off)
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = gid >> 2, leg = gid & 3;
@@ -291,7 +292,9 @@ __global__ __launch_bounds__(256) void plan_kernel(const mpcqp_plan_params pp, c
 
   // ---- compute_grf: terrain adaptation (:335-376) ----
   double coef[3] = {0.0, 0.0, 0.0}, angle_cos = 0.0, angle = 0.0;
-  if (pp.terrain) {  // wave-uniform
+  // the reference adapts the terrain only under stance_leg_control_type == 1 (:335): with a type array the
+  // branch is per robot, i.e. uniform over the quad its four legs share, which is all the broadcasts need
+  if (pp.terrain && (!type || type[b] == 1)) {
     // the four recent contact points, to every lane of the quad (quad_perm broadcasts)
     const double x[4] = {dpp<0x00>(recent[0]), dpp<0x55>(recent[0]), dpp<0xAA>(recent[0]), dpp<0xFF>(recent[0])};
     const double y[4] = {dpp<0x00>(recent[1]), dpp<0x55>(recent[1]), dpp<0xAA>(recent[1]), dpp<0xFF>(recent[1])};
@@ -336,10 +339,10 @@ __global__ __launch_bounds__(256) void plan_kernel(const mpcqp_plan_params pp, c
 int plan_state_doubles() { return lp::PS_SIZE; }
 
 hipError_t launch_leg_plan(const mpcqp_plan_params& pp, double dt, double* states, const double* plan_in, int batch,
-                           double* slots, double* tq, double* out, void* stream) {
+                           double* slots, double* tq, double* out, const int* type, void* stream) {
   const int threads = 4 * batch;
   hipLaunchKernelGGL(lp::plan_kernel, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, pp, dt, states,
-                     plan_in, batch, slots, tq, out);
+                     plan_in, batch, slots, tq, out, type);
   return hipGetLastError();
 }
 

@@ -14,6 +14,11 @@
 // masks.  Whether the stored state belongs to this call's batch is decided here, on the device (the
 // host's view would be frozen into a captured graph): each part's state carries {whole batch, parts,
 // first robot, robots}, and a part whose layout differs gets the identity order.
+//
+// A typed solve (LaunchArgs::type) selects robots here: a robot whose type differs from the wanted one is
+// left out of the sort, its key[] and contacts[] entries are not touched, and the places behind the
+// selected robots get the index -1, for which wave_kernel solves nothing.  With the hint off such a call
+// still needs an order[]: identity_kernel writes the identity with holes and reads or writes no state.
 #include "mpcqp_internal.h"
 
 namespace mpcqp {
@@ -26,8 +31,10 @@ static_assert(NBIN <= 128, "order_kernel matches bins over 7 bits");
 __global__ __launch_bounds__(ONT) void order_kernel(const double* __restrict__ recs, int rec_doubles, int robots,
                                                     int* __restrict__ order, const int* __restrict__ key,
                                                     int* __restrict__ contacts, int* __restrict__ layout,
-                                                    int whole, int parts, int part, int first, int kmax) {
+                                                    int whole, int parts, int part, int first, int kmax,
+                                                    const int* __restrict__ type, int want) {
   __shared__ int start[NBIN];        // pass A: robots per bin; pass B: the bin's next free place
+  __shared__ int total;              // selected robots (all of them without a type array)
   __shared__ int wcount[ONW][NBIN];  // pass B: robots per bin of each wave of the current chunk
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const bool valid = layout[0] == whole && layout[1] == parts && layout[2] == first && layout[3] == robots;
@@ -49,10 +56,12 @@ __global__ __launch_bounds__(ONT) void order_kernel(const double* __restrict__ r
     for (int l = 0; l < MPCQP_NUM_LEG; ++l) m |= (c[l] != 0.0) ? (1 << l) : 0;
     return m;
   };
+  auto selected = [&](int r) { return !type || type[r] == want; };
   if (!valid) {
     for (int r = t; r < robots; r += ONT) {
-      order[r] = r;
-      contacts[r] = mask_of(r);
+      const bool sel = selected(r);
+      order[r] = sel ? r : -1;
+      if (sel) contacts[r] = mask_of(r);
     }
     return;
   }
@@ -62,11 +71,13 @@ __global__ __launch_bounds__(ONT) void order_kernel(const double* __restrict__ r
     return (m != contacts[r] ? 0 : ORDER_KEY_MAX + 1) + (ORDER_KEY_MAX - kc);
   };
   // pass A: robots per bin, then each bin's first place
-  for (int r = t; r < robots; r += ONT) atomicAdd(&start[bin_of(r, mask_of(r))], 1);
+  for (int r = t; r < robots; r += ONT)
+    if (selected(r)) atomicAdd(&start[bin_of(r, mask_of(r))], 1);
   __syncthreads();
   int before = 0;
   if (t < NBIN)
     for (int b = 0; b < t; ++b) before += start[b];
+  if (t == NBIN - 1) total = before + start[t];
   __syncthreads();
   if (t < NBIN) start[t] = before;
   __syncthreads();
@@ -74,7 +85,7 @@ __global__ __launch_bounds__(ONT) void order_kernel(const double* __restrict__ r
   // the bin's robots in the chunk's earlier waves, plus those in earlier lanes of its own wave
   for (int c0 = 0; c0 < robots; c0 += ONT) {
     const int r = c0 + t;
-    const bool act = r < robots;
+    const bool act = r < robots && selected(r);
     const int m = act ? mask_of(r) : 0;
     const int bin = act ? bin_of(r, m) : 0;
     unsigned long long peers = __ballot(act);  // the wave's lanes in the same bin
@@ -104,17 +115,32 @@ __global__ __launch_bounds__(ONT) void order_kernel(const double* __restrict__ r
     for (int e = t; e < ONW * NBIN; e += ONT) (&wcount[0][0])[e] = 0;
     __syncthreads();
   }
+  // the places behind the selected robots: nothing to solve
+  for (int pos = total + t; pos < robots; pos += ONT) order[pos] = -1;
+}
+
+// A typed solve without the hint: the identity with holes.
+__global__ __launch_bounds__(256) void identity_kernel(int robots, int* __restrict__ order,
+                                                       const int* __restrict__ type, int want) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < robots) order[r] = type[r] == want ? r : -1;
 }
 
 }  // namespace ord
 
 hipError_t launch_order(const LaunchArgs& a, int kmax) {
   const OrderHint& o = a.hint;
+  if (o.identity) {
+    if (!o.order || !a.type || a.batch < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ord::identity_kernel, dim3((a.batch + 255) / 256), dim3(256), 0, (hipStream_t)a.stream,
+                       a.batch, o.order, a.type, a.want);
+    return hipGetLastError();
+  }
   if (!o.order || !o.key || !o.contacts || !o.layout || a.batch < 1 || o.parts < 1 || kmax > ord::ONT)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(ord::order_kernel, dim3(1), dim3(ord::ONT), 0, (hipStream_t)a.stream, a.recs,
                      MPCQP_REC_SIZE(a.p.horizon), a.batch, o.order, o.key, o.contacts, o.layout, o.whole, o.parts,
-                     o.part, o.first, kmax);
+                     o.part, o.first, kmax, a.type, a.want);
   return hipGetLastError();
 }
 

@@ -85,7 +85,8 @@ template <int N>
 __global__ __launch_bounds__(ScaleCfg<N>::NTS, ScaleCfg<N>::WPE) void scale_kernel(const double* __restrict__ recs, int batch,
                                                                  double* __restrict__ wstate,
                                                                  double* __restrict__ img, mpcqp_params p,
-                                                                 int* __restrict__ fb) {
+                                                                 int* __restrict__ fb, const int* __restrict__ type,
+                                                                 int want) {
   using C = Cfg<N>;
   using SC = ScaleCfg<N>;
   using WL = WarmLayout<N>;
@@ -102,6 +103,8 @@ __global__ __launch_bounds__(ScaleCfg<N>::NTS, ScaleCfg<N>::WPE) void scale_kern
   // wave_kernel's hand-off counters start at zero (stream order): [0] rank-deficient feet, [1] a KKT
   // solve that cancelled too much for its core (S_max * amp > SCHUR_AMP), [2] S_max > SCHUR_SMAX
   if (inst == 0 && t < 3) fb[t] = 0;
+  // typed solve: a robot of the other control type keeps its warm slot (the zero-pattern mask below)
+  if (type && type[inst] != want) return;
   {
     const double* rg = recs + (size_t)inst * C::REC;
     int bad = 0;
@@ -628,7 +631,7 @@ template <int N>
 static hipError_t launch_scale(const LaunchArgs& a) {
   if (!a.fallback) return hipErrorInvalidValue;
   hipLaunchKernelGGL((wv::scale_kernel<N>), dim3(a.batch), dim3(wv::ScaleCfg<N>::NTS), 0, (hipStream_t)a.stream,
-                     a.recs, a.batch, a.wstate, a.work, a.p, a.fallback);
+                     a.recs, a.batch, a.wstate, a.work, a.p, a.fallback, a.type, a.want);
   return hipGetLastError();
 }
 hipError_t launch_scale_any(const LaunchArgs& a) {

@@ -6,10 +6,13 @@ include/mpcqp.h); this package only packs records, owns handles and calls the AB
 from . import _lib
 from ._lib import (assemble_records_device, EXPORTED, LIB_PATH, RESULT_DTYPE, MpcQpError, Params, Result, default_params,
                    load, rec_feet, rec_size, status_str)
+from .balance import assemble_balance, assemble_balance_device, default_balance_gains, default_balance_params
+from .command import (CMD_STATE_DTYPE, CommandParams, command_device, command_state_size, default_command_params,
+                      pack_commands)
 from .estimator import (EST_OUT_DTYPE, EstimatorParams, default_estimator_params, estimator_state_size,
                         pack_estimator_slot, pack_sensors, state_estimate_device, unpack_estimator_slot)
-from .legplan import (PLAN_OUT_DTYPE, PlanParams, default_plan_params, leg_plan_device, pack_plan_inputs,
-                      plan_state_size)
+from .legplan import (PLAN_OUT_DTYPE, PlanParams, default_plan_params, leg_plan_device, leg_plan_typed_device,
+                      pack_plan_inputs, plan_state_size)
 from .records import (GO1_Q, GO1_R, RobotStates, assemble_compute_grf, assemble_test_mpc,
                       pack_states, synthetic_go1)
 from .robot_control import Go1RobotControl, RobotControl
@@ -24,4 +27,7 @@ __all__ = [
     "PLAN_OUT_DTYPE", "PlanParams", "default_plan_params", "leg_plan_device", "pack_plan_inputs", "plan_state_size",
     "EST_OUT_DTYPE", "EstimatorParams", "default_estimator_params", "estimator_state_size", "pack_estimator_slot",
     "pack_sensors", "state_estimate_device", "unpack_estimator_slot",
+    "CMD_STATE_DTYPE", "CommandParams", "command_device", "command_state_size", "default_command_params",
+    "pack_commands", "assemble_balance", "assemble_balance_device", "default_balance_gains",
+    "default_balance_params", "leg_plan_typed_device",
 ]

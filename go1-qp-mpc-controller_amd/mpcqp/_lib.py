@@ -41,6 +41,10 @@ PLAN_CONTACT_WINDOW, PLAN_TERRAIN_WINDOW = 60, 100
 SN_QUAT, SN_JOINT_POS, SN_JOINT_VEL, SN_IMU_ACC, SN_IMU_ANG_VEL, SN_SIZE = 0, 4, 16, 28, 31, 36
 EO_FOOT_POS_REL, EO_FOOT_VEL_REL, EO_FOOT_VEL_ABS, EO_CONTACT_W, EO_X, EO_DIAG_P, EO_DET = 0, 12, 24, 36, 40, 58, 76
 EO_SIZE = 80
+BAL_SIZE = 72  # balance record (include/mpcqp.h MPCQP_BAL_*; the offsets are balance.BAL_*)
+# command stage: command row and slot (include/mpcqp.h MPCQP_CM_*, MPCQP_CS_*)
+CM_VEL, CM_RATE, CM_MODE_REQUEST, CM_SIZE = 0, 3, 6, 8
+CS_INIT, CS_BODY_HEIGHT, CS_CTRL_STATE, CS_PREV_CTRL_STATE, CS_KP_LINEAR, CS_SIZE = 0, 1, 2, 3, 4, 8
 
 
 def rec_feet(N):
@@ -85,6 +89,20 @@ class BalanceParams(ctypes.Structure):
     """mpcqp_balance_params."""
     _fields_ = [("q_diag", ctypes.c_double * 6), ("r", ctypes.c_double), ("mu", ctypes.c_double),
                 ("f_min", ctypes.c_double), ("f_max", ctypes.c_double)]
+
+
+class BalanceGains(ctypes.Structure):
+    """mpcqp_balance_gains."""
+    _fields_ = [("kp_linear", ctypes.c_double * 3), ("kd_linear", ctypes.c_double * 3),
+                ("kp_angular", ctypes.c_double * 3), ("kd_angular", ctypes.c_double * 3)]
+
+
+class CommandParams(ctypes.Structure):
+    """mpcqp_command_params."""
+    _fields_ = [("body_height_init", ctypes.c_double), ("body_height_max", ctypes.c_double),
+                ("body_height_min", ctypes.c_double), ("vel_lock_threshold", ctypes.c_double),
+                ("kp_linear", ctypes.c_double * 3), ("kp_linear_lock_x", ctypes.c_double),
+                ("kp_linear_lock_y", ctypes.c_double)]
 
 
 class PlanParams(ctypes.Structure):
@@ -147,6 +165,9 @@ EXPORTED = [
     "mpcqp_plan_default_params", "mpcqp_plan_state_size", "mpcqp_leg_plan_device",
     "mpcqp_est_default_params", "mpcqp_est_params_size", "mpcqp_estimator_state_size",
     "mpcqp_state_estimate_device",
+    "mpcqp_command_default_params", "mpcqp_command_state_size", "mpcqp_command_device",
+    "mpcqp_balance_default_gains", "mpcqp_assemble_balance_device",
+    "mpcqp_balance_solve_typed_device", "mpcqp_solve_batch_warm_typed_device", "mpcqp_leg_plan_typed_device",
 ]
 
 _libs = {}
@@ -248,6 +269,23 @@ def load(debug=False):
     L.mpcqp_state_estimate_device.argtypes = [ctypes.POINTER(EstimatorParams), ctypes.c_double, vp, vp, vp, i32, vp,
                                               vp, vp, vp]
     L.mpcqp_state_estimate_device.restype = i32
+    L.mpcqp_command_default_params.argtypes = [ctypes.POINTER(CommandParams)]
+    L.mpcqp_command_default_params.restype = None
+    L.mpcqp_command_state_size.argtypes = []
+    L.mpcqp_command_state_size.restype = i32
+    L.mpcqp_command_device.argtypes = [ctypes.POINTER(CommandParams), ctypes.c_double, vp, vp, vp, i32, vp, vp]
+    L.mpcqp_command_device.restype = i32
+    L.mpcqp_balance_default_gains.argtypes = [ctypes.POINTER(BalanceGains)]
+    L.mpcqp_balance_default_gains.restype = None
+    L.mpcqp_assemble_balance_device.argtypes = [ctypes.POINTER(BalanceGains), vp, vp, vp, i32, vp, vp]
+    L.mpcqp_assemble_balance_device.restype = i32
+    L.mpcqp_balance_solve_typed_device.argtypes = [vp, ctypes.POINTER(BalanceParams), vp, i32, vp, i32, vp, vp]
+    L.mpcqp_balance_solve_typed_device.restype = i32
+    L.mpcqp_solve_batch_warm_typed_device.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.mpcqp_solve_batch_warm_typed_device.restype = i32
+    L.mpcqp_leg_plan_typed_device.argtypes = [ctypes.POINTER(PlanParams), ctypes.c_double, vp, vp, i32, vp, vp, vp,
+                                              vp, vp]
+    L.mpcqp_leg_plan_typed_device.restype = i32
     if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
         raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
                          f"{ctypes.sizeof(EstimatorParams)} in ctypes")

@@ -6,9 +6,11 @@ with a fresh OsqpEigen solver.  ``assemble_balance`` packs the ``*CtrlStates`` f
 reads into the MPCQP_BAL_* record of include/mpcqp.h; the root acceleration, H, g, bounds and the
 OSQP solve all run on the device (``MpcQpSolver.balance_solve_device``).
 """
+import ctypes
+
 import numpy as np
 
-from ._lib import default_balance_params  # noqa: F401  (re-export)
+from ._lib import BalanceGains, check, default_balance_params, load  # noqa: F401  (default_balance_params: re-export)
 from .records import GO1_MASS, RobotStates
 
 BAL_POS, BAL_POS_D, BAL_ROT, BAL_ROT_Z = 0, 3, 6, 15
@@ -56,3 +58,27 @@ def assemble_balance(s: RobotStates, kp_linear=GO1_KP_LINEAR, kd_linear=GO1_KD_L
     rec[:, BAL_FEET:BAL_FEET + 12] = np.asarray(s.foot_pos_abs).reshape(B, 12)
     rec[:, BAL_CONTACTS:BAL_CONTACTS + 4] = np.asarray(s.contacts, dtype=np.float64)
     return rec
+
+
+def default_balance_gains(**over):
+    """mpcqp_balance_default_gains (Go1CtrlStates.hpp:279-302, the GO1_* values above) + keyword overrides
+    (each a sequence of 3)."""
+    g = BalanceGains()
+    load().mpcqp_balance_default_gains(ctypes.byref(g))
+    for k, v in over.items():
+        arr = getattr(g, k)
+        flat = np.asarray(v, dtype=np.float64).reshape(-1)
+        if flat.size != 3:
+            raise ValueError(f"{k}: expected 3 values, got {flat.size}")
+        for i, x in enumerate(flat):
+            arr[i] = float(x)
+    return g
+
+
+def assemble_balance_device(gains, d_states, d_plan_in, d_cmd_state, batch, d_bal_records, stream=0):
+    """mpcqp_assemble_balance_device on device pointers (ints): the MPCQP_BAL_* records from the MPCQP_ST_* rows,
+    root_rot_mat_z of the MPCQP_PL_* rows, the gains and, with d_cmd_state nonzero, the command slots'
+    kp_linear (0: gains.kp_linear).  Bitwise assemble_balance."""
+    check(load().mpcqp_assemble_balance_device(ctypes.byref(gains), d_states, d_plan_in, d_cmd_state or None,
+                                               int(batch), d_bal_records, stream or None),
+          None, "mpcqp_assemble_balance_device")

@@ -75,3 +75,12 @@ def leg_plan_device(plan, dt, d_states, d_plan_in, batch, d_plan_state, d_tq_rec
     check(load().mpcqp_leg_plan_device(ctypes.byref(plan), float(dt), d_states, d_plan_in, int(batch), d_plan_state,
                                        d_tq_records or None, d_plan_out or None, stream or None),
           None, "mpcqp_leg_plan_device")
+
+
+def leg_plan_typed_device(plan, dt, d_states, d_plan_in, batch, d_plan_state, d_tq_records=0, d_plan_out=0, d_type=0,
+                          stream=0):
+    """mpcqp_leg_plan_typed_device: the plan tick with the terrain adaptation only for the robots with
+    d_type[b] == 1 (A1RobotControl.cpp:335); d_type a device int32 [batch] pointer, 0 = mpcqp_leg_plan_device."""
+    check(load().mpcqp_leg_plan_typed_device(ctypes.byref(plan), float(dt), d_states, d_plan_in, int(batch),
+                                             d_plan_state, d_tq_records or None, d_plan_out or None, d_type or None,
+                                             stream or None), None, "mpcqp_leg_plan_typed_device")

@@ -126,6 +126,21 @@ class MpcQpSolver:
                                                     d_solution or None, stream or None),
               self._h, "mpcqp_solve_batch_warm_device", self._L)
 
+    def solve_warm_typed_device(self, d_records, batch, d_state, d_type, type, d_results, d_solution=0, stream=0):
+        """mpcqp_solve_batch_warm_typed_device: the warm-started solve for the robots with d_type[b] == type
+        (d_type a device int32 [batch] pointer, 0 = every robot); the others' result and solution rows,
+        warm slots and launch-order state are not written."""
+        check(self._L.mpcqp_solve_batch_warm_typed_device(self._h, d_records, int(batch), d_state, d_type or None,
+                                                          int(type), d_results, d_solution or None, stream or None),
+              self._h, "mpcqp_solve_batch_warm_typed_device", self._L)
+
+    def balance_solve_typed_device(self, bp, d_records, batch, d_type, type, d_results, stream=0):
+        """mpcqp_balance_solve_typed_device: the balance QP for the robots with d_type[b] == type (d_type a
+        device int32 [batch] pointer, 0 = every robot); the others' result rows are not written."""
+        check(self._L.mpcqp_balance_solve_typed_device(self._h, ctypes.byref(bp), d_records, int(batch),
+                                                       d_type or None, int(type), d_results, stream or None),
+              self._h, "mpcqp_balance_solve_typed_device", self._L)
+
     @property
     def scale_image_size(self):
         return int(self._L.mpcqp_debug_scale_image_doubles(self.params.horizon))

@@ -18,17 +18,36 @@ and IMU callbacks, GazeboA1ROS.cpp:242-307, and A1BasicEKF::update_estimation, A
 root_euler, root_pos, root_ang_vel, root_lin_vel, root_rot_mat and foot_pos_abs of ``states``,
 root_rot_mat_z of ``plan_in`` and j_foot of ``tq_records`` are computed on the device from ``sensors``
 (quaternion, joint angles and rates, IMU sample) and the foot forces of ``plan_in``, so the caller writes
-only sensor-level state.  The estimator runs first: the plan and the solve see this tick's estimate.
+only sensor-level state.  The estimator runs before the plan: the plan and the solve see this tick's estimate.
+
+With ``command`` (a CommandParams) it starts with the command stage (the joystick command block of
+main_update, GazeboA1ROS.cpp:122-188): the desired velocities, root_euler_d, root_pos_d and movement_mode
+of ``states`` / ``plan_in`` and the position-locked kp_linear of ``cmd_state`` are computed on the device
+from the joystick-level rows ``cmd``.  It runs first, as in the reference: the estimator sees this tick's
+movement_mode, and the position lock reads the previous tick's root_pos.
+
+With ``control_type`` each robot takes the stance_leg_control_type branch of its own (A1RobotControl.cpp:377
+QP balance controller, :446 MPC): the tick assembles both kinds of record and runs the balance solve of the
+type-0 robots and the warm MPC solve of the type-1 robots into the one ``results`` buffer, so the stage order
+is command -> estimate -> plan -> assemble (MPC and balance) -> balance solve -> warm MPC solve -> torque map.
 """
 from . import _lib
+from .balance import assemble_balance_device, default_balance_gains
+from .command import command_device, command_state_size
 from .estimator import estimator_state_size, state_estimate_device
-from .legplan import leg_plan_device, plan_state_size
+from .legplan import leg_plan_device, leg_plan_typed_device, plan_state_size
 from .solver import MpcQpSolver
 from .torques import joint_torques_device
 
 
 class ControlTick:
-    def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None):
+    def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None, command=None,
+                 control_type=None, balance=None, gains=None):
+        """control_type: None = the MPC-only tick; 0 / 1 = every robot takes the balance / the MPC branch;
+        "per_robot" = the tick owns ``self.control_type``, an int32 [B] device tensor the caller writes
+        (initialised to 1) and every kernel reads when it runs, so a replayed graph follows it.  A robot whose
+        type is neither 0 nor 1 is solved by neither branch and keeps its previous ``results`` row.
+        ``balance`` (BalanceParams) and ``gains`` (BalanceGains) default to the reference's."""
         import torch
         self.torch = torch
         self.B = int(batch)
@@ -60,21 +79,65 @@ class ControlTick:
             self.sensors = torch.zeros((self.B, _lib.SN_SIZE), **f64)    # caller writes quat / joints / IMU here
             self.est_state = torch.zeros((self.B, estimator_state_size()), **f64)  # zero = not initialized
             self.est_out = torch.zeros((self.B, _lib.EO_SIZE), **f64)
+        self.command = command
+        if command is not None:
+            if plan is None and estimator is None:
+                if dt is None:
+                    raise ValueError("ControlTick(command=...) without plan= needs dt")
+                self.dt = float(dt)  # main_update's dt argument
+                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # movement_mode is written here
+            self.cmd = torch.zeros((self.B, _lib.CM_SIZE), **f64)       # caller writes joystick-level commands here
+            self.cmd_state = torch.zeros((self.B, command_state_size()), **f64)  # zero = fresh
+        if control_type not in (None, 0, 1, "per_robot"):
+            raise ValueError('control_type must be None, 0, 1 or "per_robot"')
+        self.typed = control_type is not None
+        if self.typed:
+            self.control_type = torch.full((self.B,), 1 if control_type == "per_robot" else int(control_type),
+                                           dtype=torch.int32, device=dev)
+            self.balance = balance if balance is not None else _lib.default_balance_params()
+            self.gains = gains if gains is not None else default_balance_gains()
+            self.bal_records = torch.zeros((self.B, _lib.BAL_SIZE), **f64)
+            if not hasattr(self, "plan_in"):
+                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # caller writes rot_z here
         self.graph = None
 
     def step(self, stream=None):
         """Enqueue one tick on `stream` (default: torch's current stream)."""
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        if self.command is not None:
+            command_device(self.command, self.dt, self.cmd.data_ptr(), self.states.data_ptr(),
+                           self.plan_in.data_ptr(), self.B, self.cmd_state.data_ptr(), s)
         if self.estimator is not None:
             state_estimate_device(self.estimator, self.dt, self.sensors.data_ptr(), self.plan_in.data_ptr(),
                                   self.states.data_ptr(), self.B, self.est_state.data_ptr(),
                                   self.tq_records.data_ptr(), self.est_out.data_ptr(), s)
+        if self.typed:
+            return self._step_typed(s)
         if self.plan is not None:
             leg_plan_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
                             self.plan_state.data_ptr(), self.tq_records.data_ptr(), self.plan_out.data_ptr(), s)
         _lib.assemble_records_device(self.solver.horizon, self.states.data_ptr(), self.B, self.records.data_ptr(), s)
         self.solver.solve_warm_device(self.records.data_ptr(), self.B, self.warm.data_ptr(), self.results.data_ptr(),
                                       0, s)
+        joint_torques_device(self.tq_records.data_ptr(), self.results.data_ptr(), self.B, self.counter.data_ptr(),
+                             self.torques.data_ptr(), s)
+
+    def _step_typed(self, s):
+        """plan -> both assemblies -> balance solve of the type-0 robots -> warm MPC solve of the type-1
+        robots -> torque map; every kernel reads ``control_type`` when it runs."""
+        ty = self.control_type.data_ptr()
+        if self.plan is not None:
+            leg_plan_typed_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
+                                  self.plan_state.data_ptr(), self.tq_records.data_ptr(), self.plan_out.data_ptr(),
+                                  ty, s)
+        _lib.assemble_records_device(self.solver.horizon, self.states.data_ptr(), self.B, self.records.data_ptr(), s)
+        assemble_balance_device(self.gains, self.states.data_ptr(), self.plan_in.data_ptr(),
+                                self.cmd_state.data_ptr() if self.command is not None else 0, self.B,
+                                self.bal_records.data_ptr(), s)
+        self.solver.balance_solve_typed_device(self.balance, self.bal_records.data_ptr(), self.B, ty, 0,
+                                               self.results.data_ptr(), s)
+        self.solver.solve_warm_typed_device(self.records.data_ptr(), self.B, self.warm.data_ptr(), ty, 1,
+                                            self.results.data_ptr(), 0, s)
         joint_torques_device(self.tq_records.data_ptr(), self.results.data_ptr(), self.B, self.counter.data_ptr(),
                              self.torques.data_ptr(), s)
 

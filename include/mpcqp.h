@@ -172,6 +172,18 @@ int32_t mpcqp_solve_batch_warm_device(mpcqp_handle* h, const double* d_records, 
  * initial value at mpcqp_create.  Returns the previous setting, or -2 for a bad argument. */
 int32_t mpcqp_set_order_hint(mpcqp_handle* h, int32_t on);
 
+/* The warm-started solve for the robots of one control type (a fleet in which each robot takes the
+ * stance_leg_control_type branch of its own, A1RobotControl.cpp:377 / :446): robot b is solved iff
+ * d_type == NULL || d_type[b] == type.  d_type is a DEVICE int32 [batch], read when the kernels run, so
+ * a captured graph follows changes made between replays.  Of a robot that is not selected nothing is
+ * written: not its mpcqp_result row, its d_solution row or its warm slot (the reference does not touch
+ * its member solver on QP ticks, :377-444), not the handle's launch-order state for it, and the hand-off
+ * counters do not count it.  A selected robot's outputs are bitwise those of
+ * mpcqp_solve_batch_warm_device on the same batch. */
+int32_t mpcqp_solve_batch_warm_typed_device(mpcqp_handle* h, const double* d_records, int32_t batch, double* d_state,
+                                            const int32_t* d_type, int32_t type, mpcqp_result* d_results,
+                                            double* d_solution, void* stream);
+
 /* Indexed copy of warm-start slots between DEVICE buffers, for callers whose solved robots are a
  * subset of their slots (a mixed-mode batch: the MPC robots' slots gathered into a compact buffer
  * for the warm solve and scattered back after it, as the reference's controller keeps its member
@@ -324,6 +336,71 @@ int32_t mpcqp_leg_plan_device(const mpcqp_plan_params* pp, double dt, double* d_
                               int32_t batch, double* d_plan_state, double* d_tq_records, double* d_plan_out,
                               void* stream);
 
+/* The same with the terrain adaptation per robot: the reference adapts the terrain only under
+ * stance_leg_control_type == 1 (A1RobotControl.cpp:335).  d_type is a DEVICE int32 [batch] read when
+ * the kernel runs; robot b runs the terrain block iff pp->terrain && d_type[b] == 1.  A robot that
+ * skips it neither advances its terrain filter nor writes MPCQP_ST_EULER_D + 1, as with terrain = 0.
+ * d_type == NULL is mpcqp_leg_plan_device. */
+int32_t mpcqp_leg_plan_typed_device(const mpcqp_plan_params* pp, double dt, double* d_states,
+                                    const double* d_plan_in, int32_t batch, double* d_plan_state,
+                                    double* d_tq_records, double* d_plan_out, const int32_t* d_type, void* stream);
+
+/* ---- command stage: the joystick command block at the top of main_update
+ * (src/a1_cpp/src/GazeboA1ROS.cpp:122-188; the same block is HardwareA1ROS.cpp:104-158): body height
+ * with its clamp, the walk / stand toggle, root_lin_vel_d / root_ang_vel_d, the root_euler_d integration,
+ * root_pos_d, movement_mode and the position lock of kp_linear.  It runs FIRST in the tick, as in the
+ * reference: the estimator sees this tick's movement_mode, and the position lock reads the previous
+ * tick's root_pos (the reference runs the estimator after this block, GazeboA1ROS.cpp:190-198).      */
+typedef struct mpcqp_command_params {
+  double body_height_init;   /* joy_cmd_body_height = 0.2 (GazeboA1ROS.h:133)                         */
+  double body_height_max;    /* JOY_CMD_BODY_HEIGHT_MAX 0.32 (A1Params.h:16)                          */
+  double body_height_min;    /* JOY_CMD_BODY_HEIGHT_MIN 0.1 (A1Params.h:17)                           */
+  double vel_lock_threshold; /* 0.05 (GazeboA1ROS.cpp:180)                                            */
+  double kp_linear[3];       /* 100, 100, 300 (Go1CtrlStates.hpp:279-281)                             */
+  double kp_linear_lock_x;   /* 100 (Go1CtrlStates.hpp:304)                                           */
+  double kp_linear_lock_y;   /* 100 (Go1CtrlStates.hpp:305)                                           */
+} mpcqp_command_params;
+
+void mpcqp_command_default_params(mpcqp_command_params* p);
+
+/* Command row, one per robot, written by the caller (offsets in doubles).  The values are the joy_cmd_*
+ * members, already scaled by the JOY_CMD_*_MAX constants as joy_callback does at sensor rate
+ * (GazeboA1ROS.cpp:390-416); that scaling stays with the caller, like the IMU moving averages.      */
+#define MPCQP_CM_VEL 0           /* [3] joy_cmd_velx, joy_cmd_vely, joy_cmd_velz                      */
+#define MPCQP_CM_RATE 3          /* [3] joy_cmd_roll_rate, joy_cmd_pitch_rate, joy_cmd_yaw_rate       */
+#define MPCQP_CM_MODE_REQUEST 6  /* joy_cmd_ctrl_state_change_request as 0.0 / 1.0; the stage writes
+                                    0.0 back after consuming it (:146), so one press toggles once     */
+#define MPCQP_CM_SIZE 8          /* 7 used, padded to a multiple of 4 doubles                         */
+
+/* Command slot, a caller-owned DEVICE buffer d_cmd_state [batch][mpcqp_command_state_size()] that must
+ * follow its robot from tick to tick.  Zero-filled = fresh: the first tick loads body_height_init,
+ * control state 0 and kp_linear from the parameters.  The offsets are public because
+ * mpcqp_assemble_balance_device reads MPCQP_CS_KP_LINEAR.                                           */
+#define MPCQP_CS_INIT 0             /* 0.0: fresh                                                     */
+#define MPCQP_CS_BODY_HEIGHT 1      /* joy_cmd_body_height                                            */
+#define MPCQP_CS_CTRL_STATE 2       /* joy_cmd_ctrl_state as 0.0 (stand) / 1.0 (walk)                 */
+#define MPCQP_CS_PREV_CTRL_STATE 3  /* prev_joy_cmd_ctrl_state                                        */
+#define MPCQP_CS_KP_LINEAR 4        /* [3] a1_ctrl_states.kp_linear                                   */
+#define MPCQP_CS_SIZE 8             /* 7 used, padded to a multiple of 4 doubles                      */
+int32_t mpcqp_command_state_size(void);
+
+/* One command tick for `batch` robots (DEVICE pointers, async on `stream`, no allocation and no
+ * synchronization: hipGraph-capture safe).  Chain it before mpcqp_state_estimate_device on the same
+ * stream.  In the reference's statement order (GazeboA1ROS.cpp:124-188): height += velz * dt and the two
+ * clamps; prev = state and the toggle; MPCQP_ST_LIN_VEL_D and MPCQP_ST_ANG_VEL_D from the row;
+ * MPCQP_ST_EULER_D += rate * dt IN PLACE (root_euler_d lives in the caller's row from tick to tick, so
+ * the plan stage's terrain write of MPCQP_ST_EULER_D + 1 is what the next tick integrates from, as in
+ * the reference); MPCQP_ST_POS_D + 2 = height; movement_mode into MPCQP_PL_MOVEMENT_MODE of d_plan_in;
+ * the leave-walking lock (:167-173) and the walking-mode lock (:179-188), which refresh
+ * MPCQP_ST_POS_D[0:2] from MPCQP_ST_POS and switch kp_linear[0:2] of the slot; 0.0 into
+ * MPCQP_CM_MODE_REQUEST of d_cmd.  Nothing else is written.  Multiplies and adds are not contracted.
+ * A robot whose command row (its 7 used doubles) is non-finite keeps its slot, its command row, its
+ * movement_mode, MPCQP_ST_EULER_D, _POS_D and _ANG_VEL_D, and gets NaN in MPCQP_ST_LIN_VEL_D only, a
+ * field rewritten every tick: that tick's solve reports MPCQP_STATUS_NAN_INPUT for it alone and the
+ * next finite row recovers. */
+int32_t mpcqp_command_device(const mpcqp_command_params* cp, double dt, double* d_cmd, double* d_states,
+                             double* d_plan_in, int32_t batch, double* d_cmd_state, void* stream);
+
 /* ---- state front end: what the reference computes between the sensor callbacks and the plan,
  *   pose callback   src/a1_cpp/src/GazeboA1ROS.cpp:242-289 (root_rot_mat, root_euler, root_rot_mat_z:
  *                   :265-269 with Utils::quat_to_euler, utils/Utils.cpp:7-33; leg forward kinematics,
@@ -442,7 +519,34 @@ void mpcqp_balance_default_params(mpcqp_balance_params* p);
  * guard in this branch, :440-443: a NaN solution stays NaN and sets nan_legs). */
 int32_t mpcqp_balance_solve_device(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* d_records,
                                    int32_t batch, mpcqp_result* d_results, void* stream);
-/* Host-pointer convenience wrapper of the above (copies in, solves, copies out, synchronizes). */
+/* The same for the robots of one control type: robot b is solved iff d_type == NULL || d_type[b] == type
+ * (d_type a DEVICE int32 [batch], read when the kernel runs).  The mpcqp_result row of a robot that is
+ * not selected is not written; a selected robot's row is bitwise mpcqp_balance_solve_device's. */
+int32_t mpcqp_balance_solve_typed_device(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* d_records,
+                                         int32_t batch, const int32_t* d_type, int32_t type, mpcqp_result* d_results,
+                                         void* stream);
+
+/* The PD gains of the balance branch's root_acc (A1RobotControl.cpp:380-390). */
+typedef struct mpcqp_balance_gains {
+  double kp_linear[3];  /* 100, 100, 300 (Go1CtrlStates.hpp:279-281)  */
+  double kd_linear[3];  /* 70, 70, 120 (Go1CtrlStates.hpp:286-288)    */
+  double kp_angular[3]; /* 150, 150, 1 (Go1CtrlStates.hpp:293-295)    */
+  double kd_angular[3]; /* 4.5, 4.5, 30 (Go1CtrlStates.hpp:300-302)   */
+} mpcqp_balance_gains;
+
+void mpcqp_balance_default_gains(mpcqp_balance_gains* g);
+
+/* Replaces the host packing of the MPCQP_BAL_* record (the fields A1RobotControl.cpp:321-332, :377-444
+ * read from the controller state) for `batch` robots: d_states [batch][MPCQP_ST_SIZE], MPCQP_PL_ROT_Z of
+ * d_plan_in [batch][MPCQP_PL_SIZE], the gains, and kp_linear from MPCQP_CS_KP_LINEAR of d_cmd_state
+ * [batch][MPCQP_CS_SIZE] (NULL: gains->kp_linear) -> d_bal_records [batch][MPCQP_BAL_SIZE].  Pure copies
+ * (contacts as given; the padding is written 0).  DEVICE pointers, async on `stream`, capture safe.
+ * Chain it before mpcqp_balance_solve_device on the same stream. */
+int32_t mpcqp_assemble_balance_device(const mpcqp_balance_gains* gains, const double* d_states,
+                                      const double* d_plan_in, const double* d_cmd_state, int32_t batch,
+                                      double* d_bal_records, void* stream);
+
+/* Host-pointer convenience wrapper of mpcqp_balance_solve_device (copies in, solves, copies out, synchronizes). */
 int32_t mpcqp_balance_solve_host(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* h_records,
                                  int32_t batch, mpcqp_result* h_results);
 
