@@ -65,6 +65,15 @@ struct mpcqp_handle {
   char err[256] = {0};
 };
 
+// One packed policy network on one device (mpcqp_policy.hip): the loaded TorchScript modules of
+// Go1RLController::loadNNparams (Go1RLController.cpp:66-76) together with the controller's constants.
+struct mpcqp_policy {
+  int device = 0;
+  mpcqp::PolicyImage* d_img = nullptr;  // parameters + layer table
+  float* d_wts = nullptr;               // packed weights and biases
+  int stride0 = 0, stride1 = 0;         // row strides of the two LDS activation buffers, floats
+};
+
 namespace {
 
 // Makes the handle's device current for one entry point and restores the caller's current device
@@ -671,6 +680,123 @@ int32_t mpcqp_command_device(const mpcqp_command_params* cp, double dt, double* 
   if (batch > 0 && (!d_cmd || !d_states || !d_plan_in || !d_cmd_state)) return MPCQP_ERR_INVALID_ARG;
   if (batch == 0) return MPCQP_OK;
   return mpcqp::launch_command(*cp, dt, d_cmd, d_states, d_plan_in, batch, d_cmd_state, stream) == hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
+void mpcqp_policy_default_params(mpcqp_policy_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->n_hidden = 3;  // cpp_model.pt: 48 -> 512 -> 256 -> 128 -> 12
+  p->hidden[0] = 512;
+  p->hidden[1] = 256;
+  p->hidden[2] = 128;
+  p->servo_clamp = 0;  // Go1RLController.cpp:139-142 never clamps percent
+  p->decimation = 1;
+  for (int i = 0; i < 36; ++i) p->obs_scale[i] = 1.0;  // gravityScale_, dofPosScale_ (Go1Observation.hpp:54, :59)
+  for (int i = 0; i < 3; ++i) {
+    p->obs_scale[i] = 2.0;       // linVelScale_ (:52)
+    p->obs_scale[3 + i] = 0.25;  // angVelScale_ (:53)
+  }
+  p->obs_scale[9] = 2.0;  // commandScale_ (:55)
+  p->obs_scale[10] = 2.0;
+  p->obs_scale[11] = 0.25;
+  for (int i = 24; i < 36; ++i) p->obs_scale[i] = 0.05;  // dofVelScale_ (:60)
+  p->clip_obs = 100.0;      // Go1Observation.hpp:449
+  p->clip_action = 100.0;   // Go1RLController.hpp:84
+  p->action_scale = 0.25;   // Go1RLController.hpp:88
+  const double lo[3] = {-0.9425, -0.4817, -2.6285}, hi[3] = {0.9425, 2.7855, -0.9320};  // Go1RLController.cpp:36-37
+  const double kpw[3] = {20.0, 50.0, 50.0}, kdw[3] = {1.0, 2.0, 2.0};                    // :79-86
+  const double kpf[3] = {20.0, 30.0, 60.0}, kpr[3] = {20.0, 80.0, 140.0}, kds[3] = {5.0, 8.0, 12.0};  // :125-132
+  for (int leg = 0; leg < 4; ++leg) {
+    const double side = (leg & 1) ? -0.1 : 0.1;
+    p->default_joint_pos[3 * leg] = side;  // Go1CtrlStates.hpp:75-78
+    p->default_joint_pos[3 * leg + 1] = leg < 2 ? 0.8 : 1.0;
+    p->default_joint_pos[3 * leg + 2] = -1.5;
+    p->stand_pos[3 * leg] = side;  // Go1RLController.cpp:122-123
+    p->stand_pos[3 * leg + 1] = 0.6;
+    p->stand_pos[3 * leg + 2] = -1.3;
+    for (int k = 0; k < 3; ++k) {
+      p->pose_lower[3 * leg + k] = lo[k];
+      p->pose_upper[3 * leg + k] = hi[k];
+      p->kp_walk[3 * leg + k] = kpw[k];
+      p->kd_walk[3 * leg + k] = kdw[k];
+      p->kp_servo[3 * leg + k] = leg < 2 ? kpf[k] : kpr[k];
+      p->kd_servo[3 * leg + k] = kds[k];
+    }
+  }
+  p->servo_ticks = 1000.0;  // :139
+}
+
+int32_t mpcqp_policy_params_size(void) { return (int32_t)sizeof(mpcqp_policy_params); }
+
+int32_t mpcqp_policy_state_size(void) { return MPCQP_PS_SIZE; }
+
+int32_t mpcqp_policy_create(const mpcqp_policy_params* params, const float* const* h_weights,
+                            const float* const* h_biases, int32_t device, mpcqp_policy** out) {
+  if (!out) return MPCQP_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (!params || !h_weights || !h_biases) return MPCQP_ERR_INVALID_ARG;
+  mpcqp::PolicyImage img;
+  size_t n_floats = 0;
+  int s0 = 0, s1 = 0;
+  if (!mpcqp::policy_layout(*params, &img, &n_floats, &s0, &s1)) return MPCQP_ERR_INVALID_ARG;
+  if (params->decimation < 1 || !(params->servo_ticks > 0.0) || !isfinite(params->servo_ticks))
+    return MPCQP_ERR_INVALID_ARG;
+  for (int l = 0; l < img.n_layers; ++l)
+    if (!h_weights[l] || !h_biases[l]) return MPCQP_ERR_INVALID_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MPCQP_ERR_NO_DEVICE;
+  if (device < 0 || device >= ndev) return MPCQP_ERR_INVALID_ARG;
+  mpcqp_policy* pol = new (std::nothrow) mpcqp_policy();
+  float* host = new (std::nothrow) float[n_floats];
+  if (!pol || !host) {
+    delete pol;
+    delete[] host;
+    return MPCQP_ERR_ALLOC;
+  }
+  mpcqp::policy_pack(img, h_weights, h_biases, host);
+  pol->device = device;
+  pol->stride0 = s0;
+  pol->stride1 = s1;
+  DeviceGuard dg(device);
+  hipError_t e = dg.err;
+  if (e == hipSuccess) e = mpcqp::policy_reserve_lds();
+  if (e == hipSuccess) e = hipMalloc(&pol->d_img, sizeof(img));
+  if (e == hipSuccess) e = hipMalloc(&pol->d_wts, sizeof(float) * n_floats);
+  if (e == hipSuccess) e = hipMemcpy(pol->d_img, &img, sizeof(img), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(pol->d_wts, host, sizeof(float) * n_floats, hipMemcpyHostToDevice);
+  delete[] host;
+  if (e != hipSuccess) {
+    (void)hipFree(pol->d_img);
+    (void)hipFree(pol->d_wts);
+    delete pol;
+    return MPCQP_ERR_HIP;
+  }
+  *out = pol;
+  return MPCQP_OK;
+}
+
+int32_t mpcqp_policy_destroy(mpcqp_policy* p) {
+  if (!p) return MPCQP_ERR_INVALID_ARG;
+  DeviceGuard dg(p->device);
+  (void)hipFree(p->d_img);
+  (void)hipFree(p->d_wts);
+  delete p;
+  return MPCQP_OK;
+}
+
+int32_t mpcqp_policy_device(const mpcqp_policy* policy, const double* d_sensors, const double* d_states,
+                            const double* d_plan_in, const double* d_cmd, int32_t batch, double* d_policy_state,
+                            const int32_t* d_type, int32_t type, double* d_joint_torques, double* d_policy_out,
+                            void* stream) {
+  if (!policy || batch < 0) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_sensors || !d_states || !d_plan_in || !d_cmd || !d_policy_state || !d_joint_torques))
+    return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_policy(policy->d_img, policy->d_wts, policy->stride0, policy->stride1, d_sensors, d_states,
+                              d_plan_in, d_cmd, batch, d_policy_state, d_type, type, d_joint_torques, d_policy_out,
+                              stream) == hipSuccess
              ? MPCQP_OK
              : MPCQP_ERR_HIP;
 }

@@ -131,4 +131,23 @@ hipError_t launch_assemble_balance(const mpcqp_balance_gains& g, const double* s
 hipError_t launch_command(const mpcqp_command_params& cp, double dt, double* cmds, double* states, double* plan_in,
                           int batch, double* slots, void* stream);
 
+// Policy stage: the Go1 RL controller and its servo stand (mpcqp_policy.hip).  The device-resident
+// description of one policy: the parameters (read with vector loads at a lane's joint index) and, per layer,
+// the input width, the output width padded to a multiple of 32, and the float offsets of its packed weights and
+// biases in the weight image.
+struct PolicyImage {
+  mpcqp_policy_params p;
+  int n_layers;  // n_hidden + 1
+  int in[4], out[4], woff[4], boff[4];
+};
+// Fills everything of *img but the device data from p (false: inadmissible widths); the image's float count and
+// the row strides of the two LDS activation buffers.
+bool policy_layout(const mpcqp_policy_params& p, PolicyImage* img, size_t* n_floats, int* stride0, int* stride1);
+size_t policy_lds_bytes(int stride0, int stride1);
+void policy_pack(const PolicyImage& img, const float* const* h_weights, const float* const* h_biases, float* dst);
+hipError_t policy_reserve_lds();  // once per device before the first launch (not capture safe)
+hipError_t launch_policy(const PolicyImage* d_img, const float* d_wts, int stride0, int stride1, const double* sensors,
+                         const double* states, const double* plan_in, const double* cmds, int batch, double* slots,
+                         const int* type, int want, double* torques, double* outs, void* stream);
+
 }  // namespace mpcqp

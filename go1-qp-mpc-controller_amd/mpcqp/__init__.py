@@ -13,6 +13,8 @@ from .estimator import (EST_OUT_DTYPE, EstimatorParams, default_estimator_params
                         pack_estimator_slot, pack_sensors, state_estimate_device, unpack_estimator_slot)
 from .legplan import (PLAN_OUT_DTYPE, PlanParams, default_plan_params, leg_plan_device, leg_plan_typed_device,
                       pack_plan_inputs, plan_state_size)
+from .policy import (POLICY_OUT_DTYPE, POLICY_STATE_DTYPE, Policy, PolicyParams, default_policy_params,
+                     load_policy_weights, policy_device, policy_state_size)
 from .records import (GO1_Q, GO1_R, RobotStates, assemble_compute_grf, assemble_test_mpc,
                       pack_states, synthetic_go1)
 from .robot_control import Go1RobotControl, RobotControl
@@ -30,4 +32,6 @@ __all__ = [
     "CMD_STATE_DTYPE", "CommandParams", "command_device", "command_state_size", "default_command_params",
     "pack_commands", "assemble_balance", "assemble_balance_device", "default_balance_gains",
     "default_balance_params", "leg_plan_typed_device",
+    "POLICY_OUT_DTYPE", "POLICY_STATE_DTYPE", "Policy", "PolicyParams", "default_policy_params",
+    "load_policy_weights", "policy_device", "policy_state_size",
 ]

@@ -45,6 +45,9 @@ BAL_SIZE = 72  # balance record (include/mpcqp.h MPCQP_BAL_*; the offsets are ba
 # command stage: command row and slot (include/mpcqp.h MPCQP_CM_*, MPCQP_CS_*)
 CM_VEL, CM_RATE, CM_MODE_REQUEST, CM_SIZE = 0, 3, 6, 8
 CS_INIT, CS_BODY_HEIGHT, CS_CTRL_STATE, CS_PREV_CTRL_STATE, CS_KP_LINEAR, CS_SIZE = 0, 1, 2, 3, 4, 8
+# policy stage: slot and optional output row (include/mpcqp.h MPCQP_PS_*, MPCQP_PY_*)
+PS_INIT, PS_TICK, PS_SERVO_TIME, PS_MODE, PS_PREV_ACTION, PS_TARGET, PS_SIZE = 0, 1, 2, 3, 4, 16, 28
+PY_OBS, PY_RAW, PY_ACTION, PY_TARGET, PY_TORQUE, PY_STATUS, PY_UPDATED, PY_SIZE = 0, 48, 60, 72, 84, 96, 97, 100
 
 
 def rec_feet(N):
@@ -103,6 +106,19 @@ class CommandParams(ctypes.Structure):
                 ("body_height_min", ctypes.c_double), ("vel_lock_threshold", ctypes.c_double),
                 ("kp_linear", ctypes.c_double * 3), ("kp_linear_lock_x", ctypes.c_double),
                 ("kp_linear_lock_y", ctypes.c_double)]
+
+
+class PolicyParams(ctypes.Structure):
+    """mpcqp_policy_params."""
+    _fields_ = [
+        ("n_hidden", ctypes.c_int32), ("hidden", ctypes.c_int32 * 3), ("servo_clamp", ctypes.c_int32),
+        ("decimation", ctypes.c_int32), ("obs_scale", ctypes.c_double * 36), ("clip_obs", ctypes.c_double),
+        ("clip_action", ctypes.c_double), ("action_scale", ctypes.c_double),
+        ("default_joint_pos", ctypes.c_double * 12), ("pose_lower", ctypes.c_double * 12),
+        ("pose_upper", ctypes.c_double * 12), ("kp_walk", ctypes.c_double * 12), ("kd_walk", ctypes.c_double * 12),
+        ("kp_servo", ctypes.c_double * 12), ("kd_servo", ctypes.c_double * 12), ("stand_pos", ctypes.c_double * 12),
+        ("servo_ticks", ctypes.c_double),
+    ]
 
 
 class PlanParams(ctypes.Structure):
@@ -168,6 +184,8 @@ EXPORTED = [
     "mpcqp_command_default_params", "mpcqp_command_state_size", "mpcqp_command_device",
     "mpcqp_balance_default_gains", "mpcqp_assemble_balance_device",
     "mpcqp_balance_solve_typed_device", "mpcqp_solve_batch_warm_typed_device", "mpcqp_leg_plan_typed_device",
+    "mpcqp_policy_default_params", "mpcqp_policy_params_size", "mpcqp_policy_create", "mpcqp_policy_destroy",
+    "mpcqp_policy_state_size", "mpcqp_policy_device",
 ]
 
 _libs = {}
@@ -286,6 +304,23 @@ def load(debug=False):
     L.mpcqp_leg_plan_typed_device.argtypes = [ctypes.POINTER(PlanParams), ctypes.c_double, vp, vp, i32, vp, vp, vp,
                                               vp, vp]
     L.mpcqp_leg_plan_typed_device.restype = i32
+    if hasattr(L, "mpcqp_policy_device"):  # (absent from an older library given by MPCQP_LIB for an A/B)
+        fpp = ctypes.POINTER(ctypes.POINTER(ctypes.c_float))
+        L.mpcqp_policy_default_params.argtypes = [ctypes.POINTER(PolicyParams)]
+        L.mpcqp_policy_default_params.restype = None
+        L.mpcqp_policy_params_size.argtypes = []
+        L.mpcqp_policy_params_size.restype = i32
+        L.mpcqp_policy_create.argtypes = [ctypes.POINTER(PolicyParams), fpp, fpp, i32, ctypes.POINTER(vp)]
+        L.mpcqp_policy_create.restype = i32
+        L.mpcqp_policy_destroy.argtypes = [vp]
+        L.mpcqp_policy_destroy.restype = i32
+        L.mpcqp_policy_state_size.argtypes = []
+        L.mpcqp_policy_state_size.restype = i32
+        L.mpcqp_policy_device.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+        L.mpcqp_policy_device.restype = i32
+        if L.mpcqp_policy_params_size() != ctypes.sizeof(PolicyParams):
+            raise MpcQpError(f"ABI mismatch: mpcqp_policy_params is {L.mpcqp_policy_params_size()} bytes in C, "
+                             f"{ctypes.sizeof(PolicyParams)} in ctypes")
     if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
         raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
                          f"{ctypes.sizeof(EstimatorParams)} in ctypes")

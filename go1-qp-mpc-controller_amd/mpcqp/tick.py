@@ -30,24 +30,34 @@ With ``control_type`` each robot takes the stance_leg_control_type branch of its
 QP balance controller, :446 MPC): the tick assembles both kinds of record and runs the balance solve of the
 type-0 robots and the warm MPC solve of the type-1 robots into the one ``results`` buffer, so the stage order
 is command -> estimate -> plan -> assemble (MPC and balance) -> balance solve -> warm MPC solve -> torque map.
+
+With ``policy`` (a Policy) the tick ends with the policy stage, the reference's third controller (the Go1 RL
+policy and its servo stand, src/go1_rl_ctrl_cpp/src/Go1RLController.cpp:78-166): after the torque map has run
+for every robot, the stage overwrites the ``torques`` row of the robots whose control type is 2 from ``sensors``,
+``states``, ``plan_in`` and ``cmd``.  Robots of type 0 and 1 are untouched by it.
 """
 from . import _lib
 from .balance import assemble_balance_device, default_balance_gains
 from .command import command_device, command_state_size
 from .estimator import estimator_state_size, state_estimate_device
 from .legplan import leg_plan_device, leg_plan_typed_device, plan_state_size
+from .policy import policy_device, policy_state_size
 from .solver import MpcQpSolver
 from .torques import joint_torques_device
 
 
 class ControlTick:
     def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None, command=None,
-                 control_type=None, balance=None, gains=None):
+                 control_type=None, balance=None, gains=None, policy=None):
         """control_type: None = the MPC-only tick; 0 / 1 = every robot takes the balance / the MPC branch;
+        2 (with ``policy``) = every robot takes the policy branch;
         "per_robot" = the tick owns ``self.control_type``, an int32 [B] device tensor the caller writes
         (initialised to 1) and every kernel reads when it runs, so a replayed graph follows it.  A robot whose
         type is neither 0 nor 1 is solved by neither branch and keeps its previous ``results`` row.
-        ``balance`` (BalanceParams) and ``gains`` (BalanceGains) default to the reference's."""
+        ``balance`` (BalanceParams) and ``gains`` (BalanceGains) default to the reference's.
+        ``policy`` (a Policy; needs control_type "per_robot" or 2): robots of type 2 get their torques from the
+        policy stage.  The tick then owns ``policy_state`` and ``policy_out``, and ``sensors`` / ``cmd`` exist
+        even without ``estimator`` / ``command`` and are then caller-written."""
         import torch
         self.torch = torch
         self.B = int(batch)
@@ -88,8 +98,10 @@ class ControlTick:
                 self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # movement_mode is written here
             self.cmd = torch.zeros((self.B, _lib.CM_SIZE), **f64)       # caller writes joystick-level commands here
             self.cmd_state = torch.zeros((self.B, command_state_size()), **f64)  # zero = fresh
-        if control_type not in (None, 0, 1, "per_robot"):
-            raise ValueError('control_type must be None, 0, 1 or "per_robot"')
+        if control_type not in (None, 0, 1, "per_robot") and not (control_type == 2 and policy is not None):
+            raise ValueError('control_type must be None, 0, 1 or "per_robot" (or 2 with policy=)')
+        if policy is not None and control_type not in ("per_robot", 2):
+            raise ValueError('ControlTick(policy=...) needs control_type="per_robot" or 2')
         self.typed = control_type is not None
         if self.typed:
             self.control_type = torch.full((self.B,), 1 if control_type == "per_robot" else int(control_type),
@@ -99,6 +111,14 @@ class ControlTick:
             self.bal_records = torch.zeros((self.B, _lib.BAL_SIZE), **f64)
             if not hasattr(self, "plan_in"):
                 self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # caller writes rot_z here
+        self.policy = policy
+        if policy is not None:
+            if estimator is None:
+                self.sensors = torch.zeros((self.B, _lib.SN_SIZE), **f64)  # caller writes joints / IMU rate here
+            if command is None:
+                self.cmd = torch.zeros((self.B, _lib.CM_SIZE), **f64)      # caller writes the joystick velocities
+            self.policy_state = torch.zeros((self.B, policy_state_size()), **f64)  # zero = fresh
+            self.policy_out = torch.zeros((self.B, _lib.PY_SIZE), **f64)
         self.graph = None
 
     def step(self, stream=None):
@@ -124,7 +144,8 @@ class ControlTick:
 
     def _step_typed(self, s):
         """plan -> both assemblies -> balance solve of the type-0 robots -> warm MPC solve of the type-1
-        robots -> torque map; every kernel reads ``control_type`` when it runs."""
+        robots -> torque map -> policy stage of the type-2 robots; every kernel reads ``control_type`` when it
+        runs."""
         ty = self.control_type.data_ptr()
         if self.plan is not None:
             leg_plan_typed_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
@@ -140,6 +161,10 @@ class ControlTick:
                                             self.results.data_ptr(), 0, s)
         joint_torques_device(self.tq_records.data_ptr(), self.results.data_ptr(), self.B, self.counter.data_ptr(),
                              self.torques.data_ptr(), s)
+        if self.policy is not None:
+            policy_device(self.policy, self.sensors.data_ptr(), self.states.data_ptr(), self.plan_in.data_ptr(),
+                          self.cmd.data_ptr(), self.B, self.policy_state.data_ptr(), self.torques.data_ptr(),
+                          self.policy_out.data_ptr(), ty, 2, s)
 
     def capture(self):
         """Record step() as a graph.  Estimator, plan and warm slots, counters and torques keep evolving on replay,

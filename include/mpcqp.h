@@ -550,6 +550,99 @@ int32_t mpcqp_assemble_balance_device(const mpcqp_balance_gains* gains, const do
 int32_t mpcqp_balance_solve_host(mpcqp_handle* h, const mpcqp_balance_params* bp, const double* h_records,
                                  int32_t batch, mpcqp_result* h_results);
 
+/* ---- policy stage: the reference's third controller, the Go1 learned walking policy with its servo
+ * stand (src/go1_rl_ctrl_cpp): per robot and per tick
+ *   observation     observation/Go1Observation.hpp:152-166, cast to float32 with the previous action
+ *                   appended (Go1RLController.cpp:95-96)
+ *   network         the TorchScript MLP of TorchEigen::run (Go1RLController.cpp:98), 48 -> hidden -> 12,
+ *                   ELU, float32
+ *   action          clip, prev_action, scale, default pose, pose limits (:99-109)
+ *   servo stand     advance_servo (:121-146)
+ *   motor law       tau = Kp (target - q) - Kd dq with the gains of the mode that ran (:79-86, :125-132).
+ *                   The reference sends the LowCmd (q = target, dq = 0, tau = 0, :149-166) and leaves this
+ *                   line to the motor controller; the tick's output is joint torques, so the stage applies it.
+ * The robot's mode is MPCQP_PL_MOVEMENT_MODE, as SwitchController's toggle sets it (MainGazebo.cpp:74-83):
+ * 1.0 runs advance, anything else advance_servo.  The hardware variant's observation, the C++ call surface
+ * and the ROS debug topics are not built; updateHistory (Go1Observation.hpp:172-181) is dead code there.  */
+typedef struct mpcqp_policy mpcqp_policy; /* device-resident packed weights and parameters */
+
+typedef struct mpcqp_policy_params {
+  int32_t n_hidden;             /* hidden layers, 1..3; 3 (cpp_model.pt)                                  */
+  int32_t hidden[3];            /* their widths, each a multiple of 32 and <= 512; 512, 256, 128          */
+  int32_t servo_clamp;          /* 0 (the reference: percent grows past 1, :139-142); 1 clamps it to 1   */
+  int32_t decimation;           /* ticks per action update; 1 (parameters.yaml:9-11 is 2)                 */
+  double obs_scale[36];         /* scaleFactor_: 2 x3, 0.25 x3, 1 x3, (2, 2, 0.25), 1 x12, 0.05 x12
+                                   (Go1Observation.hpp:52-63)                                             */
+  double clip_obs;              /* clipObs_ = 100 (Go1Observation.hpp:449)                                */
+  double clip_action;           /* clipAction_ = 100 (Go1RLController.hpp:84)                             */
+  double action_scale;          /* actionScale_ = 0.25 (Go1RLController.hpp:88)                           */
+  double default_joint_pos[12]; /* (+-0.1, 0.8 front / 1.0 rear, -1.5) (Go1CtrlStates.hpp:75-78)          */
+  double pose_lower[12];        /* clipPoseLower_ (-0.9425, -0.4817, -2.6285) (Go1RLController.cpp:36)    */
+  double pose_upper[12];        /* clipPoseUpper_ (0.9425, 2.7855, -0.9320) (:37)                         */
+  double kp_walk[12];           /* (20, 50, 50) per leg (:79-82)                                          */
+  double kd_walk[12];           /* (1, 2, 2) per leg (:83-86)                                             */
+  double kp_servo[12];          /* (20, 30, 60) front, (20, 80, 140) rear (:125-128)                      */
+  double kd_servo[12];          /* (5, 8, 12) per leg (:129-132)                                          */
+  double stand_pos[12];         /* (+-0.1, 0.6, -1.3) per leg (:122-123)                                  */
+  double servo_ticks;           /* 1000 (:139)                                                            */
+} mpcqp_policy_params;
+
+void mpcqp_policy_default_params(mpcqp_policy_params* p);
+int32_t mpcqp_policy_params_size(void); /* sizeof(mpcqp_policy_params), for binding checks */
+
+/* Packs the network for the device once.  h_weights[l] is layer l's HOST matrix [out][in], row-major as
+ * torch.nn.Linear stores it, h_biases[l] its [out] vector, l = 0 .. n_hidden; layer 0 has 48 inputs and
+ * the last layer 12 outputs (Go1RLController.cpp:95, :34).  Allocates and copies (synchronous); the
+ * parameters are copied with the weights, so later changes to *params do not reach the policy.      */
+int32_t mpcqp_policy_create(const mpcqp_policy_params* params, const float* const* h_weights,
+                            const float* const* h_biases, int32_t device, mpcqp_policy** out);
+int32_t mpcqp_policy_destroy(mpcqp_policy* p);
+
+/* Policy slot, a caller-owned DEVICE buffer d_policy_state [batch][mpcqp_policy_state_size()] that must
+ * follow its robot from tick to tick: the members Go1RLController keeps (offsets in doubles).
+ * Zero-filled = fresh, as the constructor leaves them (Go1RLController.cpp:34-35, :50).             */
+#define MPCQP_PS_INIT 0         /* 0.0: fresh; 1.0 once the robot has run                             */
+#define MPCQP_PS_TICK 1         /* ticks run so far: an update is due when tick % decimation == 0     */
+#define MPCQP_PS_SERVO_TIME 2   /* servo_motion_time_ (:136; never reset, as in the reference)        */
+#define MPCQP_PS_MODE 3         /* the mode the last update ran: 1.0 advance, 0.0 advance_servo       */
+#define MPCQP_PS_PREV_ACTION 4  /* [12] prevActionDouble_ (:103)                                      */
+#define MPCQP_PS_TARGET 16      /* [12] targetPoses_ (:109, :141)                                     */
+#define MPCQP_PS_SIZE 28        /* a multiple of 4 doubles                                            */
+int32_t mpcqp_policy_state_size(void);
+
+/* Optional output row d_policy_out [batch][MPCQP_PY_SIZE] (NULL = skipped), offsets in doubles. */
+#define MPCQP_PY_OBS 0      /* [48] the observation the network saw, float32 values widened (:95-96)  */
+#define MPCQP_PY_RAW 48     /* [12] action_, the raw network output (:98); 0 unless this tick ran advance */
+#define MPCQP_PY_ACTION 60  /* [12] the clipped action = prev_action after this tick (:102-103)       */
+#define MPCQP_PY_TARGET 72  /* [12] targetPoses_ in force                                             */
+#define MPCQP_PY_TORQUE 84  /* [12] what was written to d_joint_torques                               */
+#define MPCQP_PY_STATUS 96  /* 0.0 ran; 1.0 a non-finite input: only this and MPCQP_PY_UPDATED are written */
+#define MPCQP_PY_UPDATED 97 /* 1.0 if this tick ran advance / advance_servo, 0.0 if it held the targets */
+#define MPCQP_PY_SIZE 100   /* 98 used, padded to a multiple of 4 doubles                             */
+
+/* One policy tick for `batch` robots (DEVICE pointers, async on `stream`, no allocation and no
+ * synchronization: hipGraph-capture safe; one kernel).  Robot b runs iff d_type == NULL || d_type[b] ==
+ * type (d_type a DEVICE int32 [batch], read when the kernel runs); of a robot that is not selected not a
+ * bit of its slot, its torques row or its output row is written.  Reads, per selected robot,
+ * MPCQP_SN_JOINT_POS, _JOINT_VEL and _IMU_ANG_VEL of d_sensors [batch][MPCQP_SN_SIZE], MPCQP_ST_LIN_VEL and
+ * MPCQP_ST_ROT of d_states [batch][MPCQP_ST_SIZE], MPCQP_PL_ROT_Z and MPCQP_PL_MOVEMENT_MODE of d_plan_in
+ * [batch][MPCQP_PL_SIZE], and joy_cmd_velx, joy_cmd_vely (MPCQP_CM_VEL) and joy_cmd_yaw_rate (MPCQP_CM_RATE
+ * + 2) of d_cmd [batch][MPCQP_CM_SIZE] (Go1Observation.hpp:152-157).
+ *   On a tick with MPCQP_PS_TICK % decimation == 0 the robot updates: mode 1.0 builds the observation in
+ * binary64 (unfused, left to right; scale, clip, cast to float32, previous action appended), runs the
+ * network in float32 (a k-ordered fused multiply-add chain per output with the bias as its start, expm1f
+ * for ELU), clips the action, stores it as prev_action and forms the targets (:99-109); any other mode
+ * advances servo_motion_time and interpolates the targets (:136-142) and keeps prev_action.  The mode
+ * that ran is stored.  On EVERY tick tau_j = Kp_j (target_j - q_j) - Kd_j dq_j with the stored targets and
+ * the stored mode's gains goes to d_joint_torques [batch][12], and the tick counter advances.
+ *   A robot with a non-finite value among the fields read above (the movement mode excepted, which is
+ * only compared with 1.0) keeps its slot and its torques row, gets MPCQP_PY_STATUS 1.0, and enters the
+ * network as a zero row, so the robots that share its tile are unaffected.                           */
+int32_t mpcqp_policy_device(const mpcqp_policy* policy, const double* d_sensors, const double* d_states,
+                            const double* d_plan_in, const double* d_cmd, int32_t batch, double* d_policy_state,
+                            const int32_t* d_type, int32_t type, double* d_joint_torques, double* d_policy_out,
+                            void* stream);
+
 const char* mpcqp_status_str(int32_t status);
 const char* mpcqp_error_str(int32_t err);
 /* Last HIP error string recorded by the handle (for MPCQP_ERR_HIP). */
