@@ -851,9 +851,10 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
 // AMP (update_info iterations): amp = max|R'^-1 w| / max|u| over the robot's variables, the
 // cancellation of the push-through identity u = R'^-1 w - B'(I - S^-1)B w in this solve: the rounding
 // errors of both terms (and of S^-1) reach u amplified by it.
-template <int N, int R, bool AMP = false>
+// mark_q(): the caller's phase mark between the store of q and the u phase (nothing in product builds).
+template <int N, int R, bool AMP = false, class MarkQ>
 __device__ __forceinline__ void schur_solve(SchurLds<N>& F, const double (&W)[R], const double (&RI)[R][3],
-                                            const bool (&vvr)[R], double (&U)[R], double& amp) {
+                                            const bool (&vvr)[R], double (&U)[R], double& amp, MarkQ&& mark_q) {
   constexpr int NI = SchurCfg<N>::NI, QS = SchurCfg<N>::QS, BS = SchurCfg<N>::BS;
   const int t = threadIdx.x, q = t >> 4, li = t & 15, leg = li >> 2, a = li & 3;
   const bool av = a < 3;
@@ -923,20 +924,47 @@ __device__ __forceinline__ void schur_solve(SchurLds<N>& F, const double (&W)[R]
   mv16<false>(z1, c1, a0, a1, a2, a3);
   load(c1, 3);
   mv16<false>(z2, c0, a0, a1, a2, a3);
+  // The u phase's columns of B do not depend on q (B changes only at a factorization): every round's
+  // six are issued here, into the registers Q's chunk 2 has left, and return behind the last block's
+  // FMAs instead of one dependent LDS round trip each after q (at one wave per SIMD nothing hides
+  // those).  sched_barrier keeps them above the block, keep() above the hand-off.
+  double bc[R][6];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int kk = 4 * r + ig;
+    const int kc = kk < N ? kk : N - 1;
+    const double* bp = &F.Bm[6 * kc][idx];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) bc[r][e] = bp[e * BS];
+  }
+  __builtin_amdgcn_sched_barrier(0);
   mv16<false>(z3, c1, a0, a1, a2, a3);
   const double qi = (a0 + a1) + (a2 + a3);
   if (t < NI) F.qv[t] = qi;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int e = 0; e < 6; ++e) keep(bc[r][e]);
   wave_sync();
-  // variable role: u = R'^-1 w - B' q (column idx of B_k from LDS)
+  mark_q();  // q stored: the u phase follows
+  // variable role: u = R'^-1 w - B' q: q of every round's step read in one batch (the compiler waits
+  // for them with counted lgkmcnt, not a drain per round; tools/isa_lds_trips.py counts the drains)
+  double2 qa[R], qb[R], qc[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int kk = 4 * r + ig;
     const int kc = kk < N ? kk : N - 1;
     const double2* q2 = reinterpret_cast<const double2*>(&F.qv[6 * kc]);
-    const double2 qa = q2[0], qb = q2[1], qc = q2[2];
-    const double* bc = &F.Bm[6 * kc][idx];
-    const double y = ((((bc[0] * qa.x + bc[BS] * qa.y) + bc[2 * BS] * qb.x) + bc[3 * BS] * qb.y) + bc[4 * BS] * qc.x) +
-                     bc[5 * BS] * qc.y;
+    qa[r] = q2[0];
+    qb[r] = q2[1];
+    qc[r] = q2[2];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const double y = ((((bc[r][0] * qa[r].x + bc[r][1] * qa[r].y) + bc[r][2] * qb[r].x) + bc[r][3] * qb[r].y) +
+                      bc[r][4] * qc[r].x) +
+                     bc[r][5] * qc[r].y;
     U[r] = r1[r] - y;
   }
   if constexpr (AMP) {

@@ -76,17 +76,27 @@ struct WSmem {
 #endif
 #define WV_MARK(id) WV_MARK_AT(id, -1)
 // cyc >= 0: a cycle count taken earlier (marks recorded in registers inside straight-line code)
-#define WV_MARK_AT(id, cyc)                                                             \
+#define WV_MARK_AT(id, cyc) WV_MARK_REC(id, cyc, WV_HWID())
+#define WV_MARK_REC(id, cyc, w3)                                                        \
   do {                                                                                  \
     if (WV_MARK_ON(id) && trace && threadIdx.x == 0 && inst < trace_cap && nmark < MPCQP_TRACE_LEN) { \
       double* tm_ = trace + ((size_t)inst * MPCQP_TRACE_LEN + nmark) * 4;                \
       tm_[0] = (id);                                                                    \
       tm_[1] = (cyc) >= 0 ? (double)(cyc) : (double)__builtin_readcyclecounter();       \
       tm_[2] = (double)__builtin_amdgcn_s_memrealtime();                                \
-      tm_[3] = WV_HWID();                                                               \
+      tm_[3] = (w3);                                                                    \
       ++nmark;                                                                          \
     }                                                                                   \
   } while (0)
+// A mark inside a phase that has no registers to spare for a record of its own: WV_STAMP takes the
+// cycle count in place, and the next mark carries it in its fourth word (WV_MARK_WITH).  The count is
+// waited for at once: a scalar load in flight would turn the LDS waits that follow into full drains.
+#define WV_STAMP(id, var)                             \
+  do {                                                \
+    var = (long long)__builtin_readcyclecounter();    \
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(var)); \
+  } while (0)
+#define WV_MARK_WITH(id, var) WV_MARK_REC(id, -1, (double)(var))
 #elif defined(MPCQP_ISA_MARKS)
 // static ISA accounting (tools/isa_phases.py): an assembly comment per phase mark
 #define WV_MARK(id) asm volatile(";WV_MARK %0" ::"n"(id))
@@ -96,12 +106,20 @@ struct WSmem {
     (void)(cyc);            \
     WV_MARK(id);            \
   } while (0)
+#define WV_STAMP(id, var) WV_MARK(id)
+#define WV_MARK_WITH(id, var) WV_MARK(id)
 #else
 #define WV_MARK(id) \
   do {              \
   } while (0)
 #define WV_MARK_AT(id, cyc) \
   do {                      \
+  } while (0)
+#define WV_STAMP(id, var) \
+  do {                    \
+  } while (0)
+#define WV_MARK_WITH(id, var) \
+  do {                        \
   } while (0)
 #endif
 
@@ -552,12 +570,19 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
     double amp = 1.0;  // the Schur form's cancellation at the update_info iteration (schur_solve)
     auto kkt = [&](auto INFO) __attribute__((always_inline)) {
       const bool tm_it = iter == 60;
+      // mark 53: q = Q z stored, 53 -> 45 being the Schur form's u phase.  Timing builds take the cycle
+      // count there and mark 45 carries it (a record of its own inside the u phase, with every round's
+      // columns of B live, is more than the register allocator takes).
+      long long cyc_q = 0;
+      (void)cyc_q;
       if (tm_it) WV_MARK(40);
       if constexpr (KS == 1) {
         double W[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) W[r] = DI[r] * RHS[r];
-        schur_solve<N, R, decltype(INFO)::value>(F, W, SRI, vvr, U, amp);
+        schur_solve<N, R, decltype(INFO)::value>(F, W, SRI, vvr, U, amp, [&]() __attribute__((always_inline)) {
+          if (tm_it) WV_STAMP(53, cyc_q);
+        });
       } else if constexpr (NOACL) {
         riccati_solve_noacl<N, R>(sm, F, DI, RHS, CAT, CAX, GADR, dtm, ig, q, leg, a, idx, tm_it, mark, U);
       } else {
@@ -686,7 +711,7 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
 #pragma unroll
         for (int r = 0; r < R; ++r) U[r] = G[r] - kx[r];
       }
-      if (tm_it) WV_MARK(45);
+      if (tm_it) WV_MARK_WITH(45, cyc_q);
     };
 
     // ---- update_x / update_z / update_y, and P~x by the KKT identity P~x~ = rhs - sigma x~ - A~'rho A~x~

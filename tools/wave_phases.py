@@ -3,10 +3,11 @@
 -DMPCQP_PHASE_TIMING (`make -C go1-qp-mpc-controller_amd variant OUT=../abtest/timing.so
 DEFS=-DMPCQP_PHASE_TIMING`, selected with MPCQP_LIB) and report median shader-clock cycles per
 robot: setup (marks 0 -> 4), each factorization (10 -> 12), the mean ADMM iteration (loop time
-minus factorizations over the iteration count) and, inside iteration 60, the KKT solve (40 -> 45),
-the ADMM update (45 -> 46) and the rest of the iteration (46 -> 47); the termination check of
-iteration 75 (48 -> 49: P~x 48 -> 50, norms and reductions 50 -> 51, termination / infeasibility
-tests and adapt_rho 51 -> 52, the rest 52 -> 49)."""
+minus factorizations over the iteration count) and, inside iteration 60, the KKT solve (40 -> 45; the
+Schur form's u phase alone 53 -> 45, mark 53's count riding in mark 45's fourth word), the ADMM
+update (45 -> 46) and the rest of the iteration (46 -> 47); the termination check of iteration 75
+(48 -> 49: P~x 48 -> 50, norms and reductions 50 -> 51, termination / infeasibility tests and
+adapt_rho 51 -> 52, the rest 52 -> 49)."""
 import argparse
 import json
 import os
@@ -42,7 +43,7 @@ def main():
         res = np.frombuffer(d_res.cpu().numpy().tobytes(), dtype=mpcqp.RESULT_DTYPE)
     ph = {k: [] for k in ("setup", "factor", "f_pre", "fp_rprime", "fp_rinv", "fp_b6r_g", "fp_chol", "fp_bvw",
                           "fp_write", "f_buildS", "f_gj", "f_post", "iter_cycles", "check75", "ck_px", "ck_norms", "ck_tests", "ck_tail", "it_kkt",
-                          "it_update", "it_rest", "kkt_a", "kkt_back", "kkt_g", "kkt_fwd", "kkt_u", "total", "shader_ghz")}
+                          "it_update", "it_rest", "kkt_q", "kkt_a", "kkt_back", "kkt_g", "kkt_fwd", "kkt_u", "total", "shader_ghz")}
     for b in range(a.traced):
         mk = marks[b]
         mk = mk[~np.isnan(mk[:, 0])]
@@ -50,6 +51,8 @@ def main():
         at = {}
         for i, c in zip(ids, cyc):
             at.setdefault(i, []).append(c)
+        # mark 53 (q = Q z stored) has no record of its own: mark 45 carries its cycle count in the fourth word
+        stamp53 = float(mk[ids == 45][0, 3]) if 45 in at else 0.0
         ph["shader_ghz"].append((cyc[-1] - cyc[0]) / max(mk[-1, 2] - mk[0, 2], 1) * 0.1)
         if 4 not in at:  # (MPCQP_PHASE_TIMING_ENDS builds: marks 0 and 20 only)
             if 20 in at:
@@ -84,6 +87,9 @@ def main():
                 ph["kkt_g"].append(at[43][0] - at[42][0])
                 ph["kkt_fwd"].append(at[44][0] - at[43][0])
                 ph["kkt_u"].append(at[45][0] - at[44][0])
+            elif stamp53 > 0:  # Schur form: w, z = B w and q = Q z (40 -> 53), then u = R'^-1 w - B'q (53 -> 45)
+                ph["kkt_q"].append(stamp53 - at[40][0])
+                ph["kkt_u"].append(at[45][0] - stamp53)
         if 48 in at and 49 in at:
             ph["check75"].append(at[49][0] - at[48][0])
         if all(k in at for k in (48, 50, 51, 52, 49)):
