@@ -847,6 +847,51 @@ int32_t mpcqp_state_estimate_device(const mpcqp_est_params* pp, double dt, const
              : MPCQP_ERR_HIP;
 }
 
+void mpcqp_plant_default_params(mpcqp_plant_params* p) {
+  if (!p) return;
+  mpcqp_est_params e;
+  mpcqp_est_default_params(&e);  // the same leg geometry, so the estimator's kinematics and the plant's agree
+  for (int i = 0; i < 4; ++i) {
+    for (int k = 0; k < 5; ++k) p->rho_fix[i][k] = e.rho_fix[i][k];
+    for (int k = 0; k < 3; ++k) p->rho_opt[i][k] = e.rho_opt[i][k];
+    p->default_joint_pos[3 * i] = 0.0;
+    p->default_joint_pos[3 * i + 1] = 0.8;
+    p->default_joint_pos[3 * i + 2] = -1.6;
+  }
+  p->mass = 13.0;  // Go1CtrlStates.hpp:145-195
+  for (int k = 0; k < 9; ++k) p->inertia[k] = 0.0;
+  p->inertia[0] = 0.0168352186;
+  p->inertia[4] = 0.0656071082;
+  p->inertia[8] = 0.0742720659;
+  p->mu = 0.6;
+  p->gravity = 9.81;
+  p->joint_inertia[0] = 0.03;  // the model's own choice, not identified from a robot description
+  p->joint_inertia[1] = 0.03;
+  p->joint_inertia[2] = 0.01;
+  for (int k = 0; k < 3; ++k) p->joint_damping[k] = 0.0;
+  p->min_height = 0.05;
+  p->substeps = 4;
+  p->pad_ = 0;
+}
+
+int32_t mpcqp_plant_params_size(void) { return (int32_t)sizeof(mpcqp_plant_params); }
+
+int32_t mpcqp_plant_state_size(void) { return MPCQP_PN_SIZE; }
+
+int32_t mpcqp_plant_step_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                int32_t batch, double* d_plant_state, const double* d_plant_init,
+                                double* d_sensors, double* d_plan_in, double* d_states, double* d_tq_records,
+                                double* d_plant_out, void* stream) {
+  if (!pp || batch < 0 || !(dt > 0.0) || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
+  if (pp->substeps < 1 || pp->substeps > 16) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_joint_torques || !d_plant_state)) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_plant(*pp, dt, d_joint_torques, batch, d_plant_state, d_plant_init, d_sensors, d_plan_in,
+                             d_states, d_tq_records, d_plant_out, stream) == hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
 void mpcqp_balance_default_params(mpcqp_balance_params* p) {
   if (!p) return;
   const double q[6] = {1.0, 1.0, 1.0, 400.0, 400.0, 100.0};  // A1RobotControl.cpp:11

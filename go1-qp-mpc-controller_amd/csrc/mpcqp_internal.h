@@ -131,6 +131,11 @@ hipError_t launch_assemble_balance(const mpcqp_balance_gains& g, const double* s
 hipError_t launch_command(const mpcqp_command_params& cp, double dt, double* cmds, double* states, double* plan_in,
                           int batch, double* slots, void* stream);
 
+// Plant stage: rigid-body model from joint torques to the next tick's sensor rows (mpcqp_plant.hip)
+hipError_t launch_plant(const mpcqp_plant_params& pp, double dt, const double* torques, int batch, double* slots,
+                        const double* init, double* sensors, double* plan_in, double* states, double* tq,
+                        double* out, void* stream);
+
 // Policy stage: the Go1 RL controller and its servo stand (mpcqp_policy.hip).  The device-resident
 // description of one policy: the parameters (read with vector loads at a lane's joint index) and, per layer,
 // the input width, the output width padded to a multiple of 32, and the float offsets of its packed weights and

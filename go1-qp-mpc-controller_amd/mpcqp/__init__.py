@@ -15,6 +15,8 @@ from .legplan import (PLAN_OUT_DTYPE, PlanParams, default_plan_params, leg_plan_
                       pack_plan_inputs, plan_state_size)
 from .policy import (POLICY_OUT_DTYPE, POLICY_STATE_DTYPE, Policy, PolicyParams, default_policy_params,
                      load_policy_weights, policy_device, policy_state_size)
+from .plant import (PLANT_OUT_DTYPE, PLANT_STATE_DTYPE, PlantParams, default_plant_params, pack_plant_init,
+                    plant_state_size, plant_step_device)
 from .records import (GO1_Q, GO1_R, RobotStates, assemble_compute_grf, assemble_test_mpc,
                       pack_states, synthetic_go1)
 from .robot_control import Go1RobotControl, RobotControl
@@ -34,4 +36,6 @@ __all__ = [
     "default_balance_params", "leg_plan_typed_device",
     "POLICY_OUT_DTYPE", "POLICY_STATE_DTYPE", "Policy", "PolicyParams", "default_policy_params",
     "load_policy_weights", "policy_device", "policy_state_size",
+    "PLANT_OUT_DTYPE", "PLANT_STATE_DTYPE", "PlantParams", "default_plant_params", "pack_plant_init",
+    "plant_state_size", "plant_step_device",
 ]

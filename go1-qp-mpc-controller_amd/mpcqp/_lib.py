@@ -48,6 +48,12 @@ CS_INIT, CS_BODY_HEIGHT, CS_CTRL_STATE, CS_PREV_CTRL_STATE, CS_KP_LINEAR, CS_SIZ
 # policy stage: slot and optional output row (include/mpcqp.h MPCQP_PS_*, MPCQP_PY_*)
 PS_INIT, PS_TICK, PS_SERVO_TIME, PS_MODE, PS_PREV_ACTION, PS_TARGET, PS_SIZE = 0, 1, 2, 3, 4, 16, 28
 PY_OBS, PY_RAW, PY_ACTION, PY_TARGET, PY_TORQUE, PY_STATUS, PY_UPDATED, PY_SIZE = 0, 48, 60, 72, 84, 96, 97, 100
+# plant stage: slot, init row and optional output row (include/mpcqp.h MPCQP_PN_*, MPCQP_PI_*, MPCQP_PT_*)
+PN_INIT, PN_POS, PN_QUAT, PN_LIN_VEL, PN_ANG_VEL, PN_JOINT_POS, PN_JOINT_VEL = 0, 1, 4, 8, 11, 14, 26
+PN_FOOT, PN_CONTACT, PN_ACC, PN_STATUS, PN_SIZE = 38, 50, 54, 57, 64
+PI_POS, PI_QUAT, PI_JOINT_POS, PI_SIZE = 0, 3, 7, 20
+PT_POS, PT_QUAT, PT_EULER, PT_LIN_VEL, PT_ANG_VEL, PT_CONTACTS, PT_GRF, PT_FOOT, PT_ACC = 0, 3, 7, 10, 13, 16, 20, 32, 44
+PT_STATUS, PT_SIZE = 47, 48
 
 
 def rec_feet(N):
@@ -147,6 +153,17 @@ class EstimatorParams(ctypes.Structure):
     ]
 
 
+class PlantParams(ctypes.Structure):
+    """mpcqp_plant_params."""
+    _fields_ = [
+        ("rho_fix", ctypes.c_double * 20), ("rho_opt", ctypes.c_double * 12), ("mass", ctypes.c_double),
+        ("inertia", ctypes.c_double * 9), ("mu", ctypes.c_double), ("gravity", ctypes.c_double),
+        ("joint_inertia", ctypes.c_double * 3), ("joint_damping", ctypes.c_double * 3),
+        ("default_joint_pos", ctypes.c_double * 12), ("min_height", ctypes.c_double),
+        ("substeps", ctypes.c_int32), ("pad_", ctypes.c_int32),
+    ]
+
+
 class Result(ctypes.Structure):
     """mpcqp_result."""
     _fields_ = [
@@ -186,6 +203,7 @@ EXPORTED = [
     "mpcqp_balance_solve_typed_device", "mpcqp_solve_batch_warm_typed_device", "mpcqp_leg_plan_typed_device",
     "mpcqp_policy_default_params", "mpcqp_policy_params_size", "mpcqp_policy_create", "mpcqp_policy_destroy",
     "mpcqp_policy_state_size", "mpcqp_policy_device",
+    "mpcqp_plant_default_params", "mpcqp_plant_params_size", "mpcqp_plant_state_size", "mpcqp_plant_step_device",
 ]
 
 _libs = {}
@@ -321,6 +339,19 @@ def load(debug=False):
         if L.mpcqp_policy_params_size() != ctypes.sizeof(PolicyParams):
             raise MpcQpError(f"ABI mismatch: mpcqp_policy_params is {L.mpcqp_policy_params_size()} bytes in C, "
                              f"{ctypes.sizeof(PolicyParams)} in ctypes")
+    if hasattr(L, "mpcqp_plant_step_device"):  # (absent from an older library given by MPCQP_LIB for an A/B)
+        L.mpcqp_plant_default_params.argtypes = [ctypes.POINTER(PlantParams)]
+        L.mpcqp_plant_default_params.restype = None
+        L.mpcqp_plant_params_size.argtypes = []
+        L.mpcqp_plant_params_size.restype = i32
+        L.mpcqp_plant_state_size.argtypes = []
+        L.mpcqp_plant_state_size.restype = i32
+        L.mpcqp_plant_step_device.argtypes = [ctypes.POINTER(PlantParams), ctypes.c_double, vp, i32, vp, vp, vp, vp,
+                                              vp, vp, vp, vp]
+        L.mpcqp_plant_step_device.restype = i32
+        if L.mpcqp_plant_params_size() != ctypes.sizeof(PlantParams):
+            raise MpcQpError(f"ABI mismatch: mpcqp_plant_params is {L.mpcqp_plant_params_size()} bytes in C, "
+                             f"{ctypes.sizeof(PlantParams)} in ctypes")
     if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
         raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
                          f"{ctypes.sizeof(EstimatorParams)} in ctypes")

@@ -35,12 +35,19 @@ With ``policy`` (a Policy) the tick ends with the policy stage, the reference's 
 policy and its servo stand, src/go1_rl_ctrl_cpp/src/Go1RLController.cpp:78-166): after the torque map has run
 for every robot, the stage overwrites the ``torques`` row of the robots whose control type is 2 from ``sensors``,
 ``states``, ``plan_in`` and ``cmd``.  Robots of type 0 and 1 are untouched by it.
+
+With ``plant`` (a PlantParams) the tick ends with the plant stage, which the reference left to Gazebo: a
+rigid-body model (single trunk, massless stance legs, joint-space swing legs, flat ground) moves every robot
+one control period on under the final ``torques`` row and writes the next tick's ``sensors`` and foot forces,
+so T replays are a T-tick closed-loop rollout with no host write in between.  Without ``estimator`` it also
+writes the ground truth of the estimator's fields into ``states`` / ``plan_in`` / ``tq_records``.
 """
 from . import _lib
 from .balance import assemble_balance_device, default_balance_gains
 from .command import command_device, command_state_size
 from .estimator import estimator_state_size, state_estimate_device
 from .legplan import leg_plan_device, leg_plan_typed_device, plan_state_size
+from .plant import plant_state_size, plant_step_device
 from .policy import policy_device, policy_state_size
 from .solver import MpcQpSolver
 from .torques import joint_torques_device
@@ -48,7 +55,7 @@ from .torques import joint_torques_device
 
 class ControlTick:
     def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None, command=None,
-                 control_type=None, balance=None, gains=None, policy=None):
+                 control_type=None, balance=None, gains=None, policy=None, plant=None, plant_init=None):
         """control_type: None = the MPC-only tick; 0 / 1 = every robot takes the balance / the MPC branch;
         2 (with ``policy``) = every robot takes the policy branch;
         "per_robot" = the tick owns ``self.control_type``, an int32 [B] device tensor the caller writes
@@ -57,7 +64,11 @@ class ControlTick:
         ``balance`` (BalanceParams) and ``gains`` (BalanceGains) default to the reference's.
         ``policy`` (a Policy; needs control_type "per_robot" or 2): robots of type 2 get their torques from the
         policy stage.  The tick then owns ``policy_state`` and ``policy_out``, and ``sensors`` / ``cmd`` exist
-        even without ``estimator`` / ``command`` and are then caller-written."""
+        even without ``estimator`` / ``command`` and are then caller-written.
+        ``plant`` (a PlantParams): the tick ends with the plant stage and owns ``plant_state``, ``plant_out`` and
+        ``plant_init`` (from the rows ``plant_init`` [B, PI_SIZE], or None: the default stance); the caller then
+        writes commands and desired values only.  Zeroing a robot's rows of ``plant_state`` and of the
+        controller's slots resets it."""
         import torch
         self.torch = torch
         self.B = int(batch)
@@ -119,6 +130,20 @@ class ControlTick:
                 self.cmd = torch.zeros((self.B, _lib.CM_SIZE), **f64)      # caller writes the joystick velocities
             self.policy_state = torch.zeros((self.B, policy_state_size()), **f64)  # zero = fresh
             self.policy_out = torch.zeros((self.B, _lib.PY_SIZE), **f64)
+        self.plant = plant
+        if plant is not None:
+            if not hasattr(self, "dt"):
+                if dt is None:
+                    raise ValueError("ControlTick(plant=...) without plan= / estimator= / command= needs dt")
+                self.dt = float(dt)  # the plant's control period
+            if not hasattr(self, "plan_in"):
+                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # the foot forces are written here
+            self.plant_state = torch.zeros((self.B, plant_state_size()), **f64)  # zero = fresh
+            self.plant_out = torch.zeros((self.B, _lib.PT_SIZE), **f64)
+            self.plant_init = None
+            if plant_init is not None:
+                rows = torch.as_tensor(plant_init, dtype=torch.float64).reshape(self.B, _lib.PI_SIZE)
+                self.plant_init = rows.to(dev).contiguous()
         self.graph = None
 
     def step(self, stream=None):
@@ -141,6 +166,26 @@ class ControlTick:
                                       0, s)
         joint_torques_device(self.tq_records.data_ptr(), self.results.data_ptr(), self.B, self.counter.data_ptr(),
                              self.torques.data_ptr(), s)
+        if self.plant is not None:
+            self._step_plant(s)
+
+    def _step_plant(self, s):
+        """The plant stage, last in the tick: the final ``torques`` row moves every robot one control period on.
+        With the estimator it writes what sensors would deliver; without it, also the truth image of what the
+        estimator would write."""
+        truth = self.estimator is None
+        plant_step_device(self.plant, self.dt, self.torques.data_ptr(), self.B, self.plant_state.data_ptr(),
+                          self.plant_init.data_ptr() if self.plant_init is not None else 0,
+                          self.sensors.data_ptr() if hasattr(self, "sensors") else 0, self.plan_in.data_ptr(),
+                          self.states.data_ptr() if truth else 0, self.tq_records.data_ptr() if truth else 0,
+                          self.plant_out.data_ptr(), s)
+
+    def prime_plant(self, stream=None):
+        """Enqueue the plant stage alone.  On fresh slots (after construction or a reset) it initialises them from
+        ``plant_init`` and writes the rows of the start without integrating, so the first tick's estimator, plan
+        and solve see the robot where it stands instead of zero rows.  (On a slot that is not fresh it is one
+        more step under the current ``torques``.)"""
+        self._step_plant(stream if stream is not None else self.torch.cuda.current_stream().cuda_stream)
 
     def _step_typed(self, s):
         """plan -> both assemblies -> balance solve of the type-0 robots -> warm MPC solve of the type-1
@@ -165,6 +210,8 @@ class ControlTick:
             policy_device(self.policy, self.sensors.data_ptr(), self.states.data_ptr(), self.plan_in.data_ptr(),
                           self.cmd.data_ptr(), self.B, self.policy_state.data_ptr(), self.torques.data_ptr(),
                           self.policy_out.data_ptr(), ty, 2, s)
+        if self.plant is not None:
+            self._step_plant(s)
 
     def capture(self):
         """Record step() as a graph.  Estimator, plan and warm slots, counters and torques keep evolving on replay,

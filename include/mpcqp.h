@@ -643,6 +643,108 @@ int32_t mpcqp_policy_device(const mpcqp_policy* policy, const double* d_sensors,
                             const int32_t* d_type, int32_t type, double* d_joint_torques, double* d_policy_out,
                             void* stream);
 
+/* ---- plant stage: a rigid-body model of the robot that turns the tick's joint torques back into the next
+ * tick's sensor rows, so a fleet closes its loop on the device (the reference closed its loop through Gazebo;
+ * this model has no counterpart there).  A single rigid trunk on massless stance legs, joint-space swing legs,
+ * flat ground z = 0:
+ *   stance leg   its foot is held where it touched down (a held foot does not slip); the joint angles follow
+ *                from the analytic inverse of the estimator's leg kinematics, the joint rates from
+ *                J^-1 (-R' v - w x p), and the joint torques act on the trunk as the ground reaction
+ *                f = -R J^-T tau (the inverse of the torque map's tau = J' (-f_grf)).  A leg whose f_z < 0
+ *                lets go; f_x, f_y are scaled onto the friction cone mu f_z.
+ *   swing leg    every joint is a free inertia, qdd = (tau - b qd) / I_j; the foot follows from the forward
+ *                kinematics and lands when it reaches z <= 0 moving down (its z is set to 0).
+ *   trunk        a = sum f / m - g, wd = I^-1 (R' sum r x f - w x I w), semi-implicit Euler in `substeps`
+ *                substeps per tick with the torque row held; the quaternion is renormalised every substep.
+ * Left out: leg mass, the swing legs' reaction on the trunk, foot slip, terrain, joint limits, and impact
+ * dynamics beyond zeroing the landing foot's velocity.  Only the feet touch the ground: a trunk that sinks to
+ * min_height is reported as fallen, it does not come to rest.  Binary64, multiplies and adds not contracted,
+ * in the statement order of tests/plant_reference.py.                                                    */
+typedef struct mpcqp_plant_params {
+  double rho_fix[4][5];         /* leg geometry, as mpcqp_est_params (the estimator's kinematics and the       */
+  double rho_opt[4][3];         /* plant's agree when these do)                                                */
+  double mass;                  /* 13 (Go1CtrlStates.hpp:145-195)                                              */
+  double inertia[9];            /* trunk inertia, body frame, row-major: diag(0.0168352186, 0.0656071082,
+                                   0.0742720659)                                                               */
+  double mu;                    /* ground friction, 0.6                                                        */
+  double gravity;               /* 9.81                                                                        */
+  double joint_inertia[3];      /* hip, thigh, calf: 0.03, 0.03, 0.01 kg m^2.  Chosen for the model's swing legs
+                                   to settle under the policy stage's walk gains; NOT identified from a robot
+                                   description                                                                 */
+  double joint_damping[3];      /* 0                                                                           */
+  double default_joint_pos[12]; /* (0, 0.8, -1.6) per leg: the pose of a fresh slot without an init row        */
+  double min_height;            /* 0.05: a trunk below it has fallen (status 2)                                */
+  int32_t substeps;             /* 4; 1..16                                                                    */
+  int32_t pad_;
+} mpcqp_plant_params;
+
+void mpcqp_plant_default_params(mpcqp_plant_params* p);
+int32_t mpcqp_plant_params_size(void); /* sizeof(mpcqp_plant_params), for bindings */
+
+/* Plant slot, a caller-owned DEVICE buffer d_plant_state [batch][mpcqp_plant_state_size()] that must follow
+ * its robot from tick to tick (offsets in doubles; FL FR RL RR leg order).  Zero-filled = fresh, the
+ * convention of every other slot: the first tick initialises it and does not integrate.  Zeroing a robot's
+ * slots (this one and the controller's) is how a fleet resets a fallen robot.                             */
+#define MPCQP_PN_INIT 0        /* 0.0: fresh                                                             */
+#define MPCQP_PN_POS 1         /* [3] trunk position, world                                              */
+#define MPCQP_PN_QUAT 4        /* [4] trunk attitude as w, x, y, z                                       */
+#define MPCQP_PN_LIN_VEL 8     /* [3] trunk linear velocity, world                                       */
+#define MPCQP_PN_ANG_VEL 11    /* [3] trunk angular velocity, body                                       */
+#define MPCQP_PN_JOINT_POS 14  /* [12] joint angles                                                      */
+#define MPCQP_PN_JOINT_VEL 26  /* [12] joint rates                                                       */
+#define MPCQP_PN_FOOT 38       /* [4][3] foot positions, world                                           */
+#define MPCQP_PN_CONTACT 50    /* [4] 1.0: the foot is held on the ground                                */
+#define MPCQP_PN_ACC 54        /* [3] trunk acceleration of the last substep, world                      */
+#define MPCQP_PN_STATUS 57     /* 0.0 fine; 1.0 a leg out of reach; 2.0 fallen: frozen until zeroed      */
+#define MPCQP_PN_SIZE 64       /* 58 used, padded to a multiple of 4 doubles                             */
+int32_t mpcqp_plant_state_size(void);
+
+/* Optional init row d_plant_init [batch][MPCQP_PI_SIZE], read on a fresh slot's first tick only. */
+#define MPCQP_PI_POS 0         /* [3] trunk position, world                                              */
+#define MPCQP_PI_QUAT 3        /* [4] trunk attitude as w, x, y, z (unit)                                */
+#define MPCQP_PI_JOINT_POS 7   /* [12] joint angles                                                      */
+#define MPCQP_PI_SIZE 20       /* 19 used, padded to a multiple of 4 doubles                             */
+
+/* Optional output row d_plant_out [batch][MPCQP_PT_SIZE], for logging and rewards. */
+#define MPCQP_PT_POS 0         /* [3] trunk position, world                                              */
+#define MPCQP_PT_QUAT 3        /* [4] trunk attitude as w, x, y, z                                       */
+#define MPCQP_PT_EULER 7       /* [3] roll, pitch, yaw (Utils::quat_to_euler)                            */
+#define MPCQP_PT_LIN_VEL 10    /* [3] world                                                              */
+#define MPCQP_PT_ANG_VEL 13    /* [3] body                                                               */
+#define MPCQP_PT_CONTACTS 16   /* [4] 0.0 / 1.0                                                          */
+#define MPCQP_PT_GRF 20        /* [4][3] ground reactions of the last substep, world; 0 for a leg off the ground */
+#define MPCQP_PT_FOOT 32       /* [4][3] foot positions, world                                           */
+#define MPCQP_PT_ACC 44        /* [3] trunk acceleration of the last substep, world                      */
+#define MPCQP_PT_STATUS 47     /* 0.0 .. 2.0 as MPCQP_PN_STATUS; 3.0 a non-finite torque row (this tick only) */
+#define MPCQP_PT_SIZE 48
+
+/* One plant tick for `batch` robots (DEVICE pointers, async on `stream`, no allocation and no
+ * synchronization: hipGraph-capture safe; one kernel).  Chain it last in the tick, after
+ * mpcqp_joint_torques_device / mpcqp_policy_device on the same stream.  Reads d_joint_torques [batch][12] and
+ * the slot, and on a fresh slot d_plant_init (NULL: identity attitude, x = y = 0, default_joint_pos, and the
+ * height at which leg 0's foot is at z = 0; all velocities zero; a foot at z <= 0 starts held at z = 0, the
+ * others in swing).  A fresh slot's tick initialises and does not integrate; every other tick runs `substeps`
+ * substeps of dt / substeps.  Each output pointer may be NULL, which skips it:
+ *   d_sensors [batch][MPCQP_SN_SIZE]   MPCQP_SN_QUAT, _JOINT_POS, _JOINT_VEL, _IMU_ACC = R' (a + (0, 0, g)) with
+ *                                      the last substep's a (+g at rest, as A1BasicEKF.cpp:76 expects),
+ *                                      _IMU_ANG_VEL = w
+ *   d_plan_in [batch][MPCQP_PL_SIZE]   MPCQP_PL_FOOT_FORCE = f_z of a held foot, else 0; MPCQP_PL_ROT_Z
+ *   d_states [batch][MPCQP_ST_SIZE]    the ground truth of what mpcqp_state_estimate_device estimates:
+ *                                      MPCQP_ST_EULER, _POS, _ANG_VEL (world), _LIN_VEL, _ROT, _FEET
+ *   d_tq_records [batch][MPCQP_TQ_SIZE] MPCQP_TQ_JFOOT
+ *   d_plant_out [batch][MPCQP_PT_SIZE]
+ * so a tick without the estimator can run on d_states / d_tq_records, and one with it on d_sensors.
+ *   A robot whose MPCQP_PN_STATUS is not 0 is frozen: not one of its doubles, in the slot or in a row, is
+ * written until its slot is zeroed.  A leg that leaves its reach (y^2 + z^2 < dd^2 or |cos knee| > 1 in the
+ * inverse kinematics) during a tick undoes that tick: the slot and the rows keep their values and status 1.0
+ * goes to MPCQP_PN_STATUS and MPCQP_PT_STATUS.  A trunk that ends a tick below min_height is written as it
+ * is, with status 2.0.  A robot whose torque row is non-finite gets 3.0 in MPCQP_PT_STATUS and nothing else
+ * written that tick, and carries on with the next finite row.                                            */
+int32_t mpcqp_plant_step_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                int32_t batch, double* d_plant_state, const double* d_plant_init,
+                                double* d_sensors, double* d_plan_in, double* d_states, double* d_tq_records,
+                                double* d_plant_out, void* stream);
+
 const char* mpcqp_status_str(int32_t status);
 const char* mpcqp_error_str(int32_t err);
 /* Last HIP error string recorded by the handle (for MPCQP_ERR_HIP). */

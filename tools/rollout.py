@@ -1,0 +1,180 @@
+"""Closed-loop rollouts of a fleet on the device: ControlTick(plant=) replayed T times with no host write in
+between, for three ticks, each under standing commands:
+
+  mpc     the MPC-only tick fed the plant's true state (no estimator; zero gravity-compensation torques, the
+          setup of tests/test_plant.py's closed loop), robots started 0.03 to 0.09 rad off level
+  full    command + estimator + plan + MPC on the plant's sensor rows, robots started 0.05 rad off level at
+          most, at the command stage's body height
+  servo   the policy stage in servo stand (control type 2; the network never runs), robots started in the
+          plant's default stance
+  servo_walk_gains   (not in the default list) the same with the walk mode's gains (20 / 50 / 50, 1 / 2 / 2) in
+          place of the servo gains
+
+Per form: ticks/s over the timed replays (HIP events around chunks of replays; the host only reads between
+chunks), how many robots ended with a plant status != 0, and how many are out of a standing envelope (tilt >
+0.3 rad, or the trunk more than 5 cm from where standing should hold it).  If any robot went wrong the form is
+run once more with a read after every tick to find the first tick at which it did.
+usage: python tools/rollout.py [--batch 4096] [--ticks 2000] [--forms mpc full servo]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "go1-qp-mpc-controller_amd"), os.path.join(REPO, "tests"),
+                os.path.join(REPO, "tools")]
+import mpcqp  # noqa: E402
+from mpcqp import _lib  # noqa: E402
+from mpcqp.tick import ControlTick  # noqa: E402
+import estimator_reference as er  # noqa: E402  (fk, to place the start poses)
+from policy_bench import seeded_weights  # noqa: E402
+from time_estimator import quat_zyx  # noqa: E402
+
+DT = 0.0025
+CHUNK = 50
+
+
+def start_rows(B, q_leg, tilt, seed):
+    """Init rows: every leg at q_leg, the trunk tilted by roll, pitch in +-tilt at a random yaw, lowered so
+    the deepest foot is 1 um under the ground (held from the start)."""
+    pp = mpcqp.default_plant_params()
+    rho_opt = np.array(pp.rho_opt).reshape(1, 4, 3)
+    rho_fix = np.array(pp.rho_fix).reshape(1, 4, 5)
+    rng = np.random.default_rng(seed)
+    e = np.stack([rng.uniform(-tilt, tilt, B), rng.uniform(-tilt, tilt, B), rng.uniform(-np.pi, np.pi, B)], 1)
+    quat = quat_zyx(e)
+    q = np.broadcast_to(np.asarray(q_leg, dtype=np.float64), (B, 4, 3))
+    rel = er.mat_vec(er.quat_to_rot(quat)[:, None], er.fk(q, rho_opt, rho_fix))
+    pos = np.stack([np.zeros(B), np.zeros(B), -rel[..., 2].min(1) - 1e-6], 1)
+    return mpcqp.pack_plant_init(pos, quat, q.reshape(B, 12)), e
+
+
+def caller_rows(k, B, pos_d, yaw, gravity_comp):
+    z = np.zeros((B, 3))
+    st = mpcqp.RobotStates(
+        root_euler=z, root_pos=z, root_ang_vel=z, root_lin_vel=z, root_rot_mat=np.zeros((B, 3, 3)),
+        root_euler_d=np.stack([z[:, 0], z[:, 0], yaw], 1), root_pos_d=pos_d, root_ang_vel_d=z, root_lin_vel_d=z,
+        foot_pos_abs=np.zeros((B, 4, 3)), contacts=np.ones((B, 4), bool), mu=np.full(B, 0.3))
+    k.states.copy_(torch.from_numpy(mpcqp.pack_states(st)))
+    kw = {} if gravity_comp else dict(torques_gravity=np.zeros(12))
+    k.tq_records.copy_(torch.from_numpy(mpcqp.assemble_torque_records(np.zeros((B, 4, 3, 3)), np.zeros((B, 4, 3)),
+                                                                      np.ones((B, 4), bool), **kw)))
+
+
+def make(form, B, seed):
+    """(tick, the height standing should hold, anything to close afterwards)."""
+    pp = mpcqp.default_plant_params()
+    if form == "mpc":
+        init, e = start_rows(B, [0.0, 0.8, -1.6], 0.09, seed)
+        k = ControlTick(B, dt=DT, plant=pp, plant_init=init)
+        caller_rows(k, B, init[:, :3], e[:, 2], False)
+        return k, init[:, 2].copy(), None
+    if form == "full":
+        h = mpcqp.default_command_params().body_height_init
+        q1 = float(np.arccos(h / (2.0 * pp.rho_fix[3])))  # both links at the same angle to the vertical
+        init, e = start_rows(B, [0.0, q1, -2.0 * q1], 0.05, seed)
+        k = ControlTick(B, plan=mpcqp.default_plan_params(), estimator=mpcqp.default_estimator_params(),
+                        command=mpcqp.default_command_params(), dt=DT, plant=pp, plant_init=init)
+        # (the command stage integrates root_euler_d from the row, so the row starts at the robot's yaw)
+        caller_rows(k, B, init[:, :3], e[:, 2], True)
+        return k, np.full(B, h), None
+    if form in ("servo", "servo_walk_gains"):
+        ws, bs = seeded_weights(0)
+        pq = mpcqp.default_policy_params()
+        if form == "servo_walk_gains":  # the servo stand with the walk mode's softer gains
+            for i in range(12):
+                pq.kp_servo[i], pq.kd_servo[i] = pq.kp_walk[i], pq.kd_walk[i]
+        pol = mpcqp.Policy(ws, bs, pq)
+        init, e = start_rows(B, [0.0, 0.8, -1.6], 0.0, seed)
+        k = ControlTick(B, dt=DT, control_type=2, policy=pol, plant=pp, plant_init=init)
+        caller_rows(k, B, init[:, :3], e[:, 2], True)
+        stand = np.array(mpcqp.default_policy_params().stand_pos).reshape(1, 4, 3)
+        rel = er.fk(stand, np.array(pp.rho_opt).reshape(1, 4, 3), np.array(pp.rho_fix).reshape(1, 4, 5))
+        return k, np.full(B, -rel[0, :, 2].mean()), pol
+    raise ValueError(form)
+
+
+def look(k, stand_z):
+    po = k.plant_out.cpu().numpy()
+    tilt = np.hypot(po[:, _lib.PT_EULER], po[:, _lib.PT_EULER + 1])
+    bad = po[:, _lib.PT_STATUS] != 0.0
+    with np.errstate(invalid="ignore"):
+        out = ~(tilt <= 0.3) | ~(np.abs(po[:, _lib.PT_POS + 2] - stand_z) <= 0.05)
+    return po, tilt, bad, out
+
+
+def run(form, B, T, seed):
+    k, stand_z, extra = make(form, B, seed)
+    try:
+        k.prime_plant()
+        k.capture()
+        torch.cuda.synchronize()
+        ms = 0.0
+        for t0 in range(0, T, CHUNK):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(min(CHUNK, T - t0)):
+                k.replay()
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms += ev[0].elapsed_time(ev[1])
+        po, tilt, bad, out = look(k, stand_z)
+        res = np.frombuffer(k.results.cpu().numpy().tobytes(), dtype=mpcqp.RESULT_DTYPE)
+        r = {"form": form, "batch": B, "ticks": T, "dt": DT, "ticks_per_s": T / (ms * 1e-3),
+             "robot_ticks_per_s": B * T / (ms * 1e-3), "ms_per_tick": ms / T,
+             "status_nonzero": int(bad.sum()), "status_counts": {str(int(s)): int((po[:, _lib.PT_STATUS] == s).sum())
+                                                                 for s in np.unique(po[:, _lib.PT_STATUS])},
+             "out_of_envelope": int((out & ~bad).sum()),
+             "tilt_max": float(np.nanmax(tilt)), "tilt_median": float(np.nanmedian(tilt)),
+             "height_median": float(np.nanmedian(po[:, _lib.PT_POS + 2])), "height_stand": float(np.median(stand_z)),
+             "contacts_mean": float(po[:, _lib.PT_CONTACTS:_lib.PT_CONTACTS + 4].sum(1).mean()),
+             "fz_over_mg_median": float(np.nanmedian(po[:, _lib.PT_GRF + 2:_lib.PT_GRF + 12:3].sum(1)) /
+                                        (k.plant.mass * k.plant.gravity))}
+        if not form.startswith("servo"):
+            r["solved_share_last_tick"] = float((res["status"] == _lib.STATUS_SOLVED).mean())
+    finally:
+        k.close()
+        if extra is not None:
+            extra.close()
+    if r["status_nonzero"] or r["out_of_envelope"]:
+        # once more, reading after every tick: the first tick at which a robot goes wrong
+        k, stand_z, extra = make(form, B, seed)
+        try:
+            k.prime_plant()
+            k.capture()
+            first_status = first_env = None
+            for t in range(1, T + 1):
+                k.replay()
+                torch.cuda.synchronize()
+                _, _, bad, out = look(k, stand_z)
+                if first_status is None and bad.any():
+                    first_status = t
+                if first_env is None and (out & ~bad).any():
+                    first_env = t
+                if first_status is not None and first_env is not None:
+                    break
+            r["first_tick_status_nonzero"] = first_status
+            r["first_tick_out_of_envelope"] = first_env
+        finally:
+            k.close()
+            if extra is not None:
+                extra.close()
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--ticks", type=int, default=2000)
+    ap.add_argument("--forms", nargs="+", default=["mpc", "full", "servo"])
+    ap.add_argument("--seed", type=int, default=1)
+    a = ap.parse_args()
+    for form in a.forms:
+        print(json.dumps(run(form, a.batch, a.ticks, a.seed)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,135 @@
+"""Time of the plant stage (mpcqp_plant_step_device) beside the torque map and the plan kernel, and of the
+graph-replayed control tick with and without it (HIP events, 3 warm-up runs, median of 20, all in one session):
+
+  plant_kernel_substeps{1,4}_ms   one launch, a standing fleet under weight-bearing torques (every leg in
+                                  stance: the inverse kinematics and three 3x3 solves per leg and substep)
+  plant_kernel_swing_substeps4_ms the same fleet in free fall (every leg in swing)
+  tick_graph_mpc_plant            ControlTick(plant=), MPC-only and truth-fed, closing its own loop
+  tick_graph_mpc                  the same tick object captured without its last stage (what the tick enqueued
+                                  before the stage existed).  Each repetition snapshots every buffer of the tick,
+                                  replays this graph, restores the snapshot and replays the closed graph, so the
+                                  two replays of a pair do the same work from the same slots but for the stage
+                                  (the solver handle's launch-order hint is the one state not restored)
+  tick_graph_full_plant / _full   the same pair for command + estimator + plan + MPC
+
+The stage's share of the tick is the median of the 20 paired differences over the median tick without it;
+each form also prints the quartiles and extremes of its 20 repetitions.
+usage: python tools/time_plant.py [--batch 4096]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "go1-qp-mpc-controller_amd"), os.path.join(REPO, "tests"),
+                os.path.join(REPO, "tools")]
+import mpcqp  # noqa: E402
+from mpcqp import _lib  # noqa: E402
+from mpcqp.tick import ControlTick  # noqa: E402
+from rollout import DT, caller_rows, start_rows  # noqa: E402
+from test_torques import torque_inputs  # noqa: E402  (synthetic Jacobians)
+from time_command import spread  # noqa: E402
+from time_estimator import RUNS, WARMUP, event_ms, median_ms  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096)
+    B = ap.parse_args().batch
+    T = WARMUP + RUNS
+    f64 = dict(dtype=torch.float64, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    out = {"batch": B, "warmup": WARMUP, "runs": RUNS}
+
+    # ---- the kernel alone ----
+    def plant_alone(substeps, stance):
+        pp = mpcqp.default_plant_params(substeps=substeps)
+        slot = torch.zeros((B, mpcqp.plant_state_size()), **f64)
+        rows = {n: torch.zeros((B, w), **f64) for n, w in (("sn", _lib.SN_SIZE), ("pl", _lib.PL_SIZE),
+                                                           ("st", _lib.ST_SIZE), ("tq", _lib.TQ_SIZE),
+                                                           ("po", _lib.PT_SIZE))}
+        tau = torch.zeros((B, 12), **f64)
+        init = None
+        if not stance:
+            pos = np.tile([0.0, 0.0, 100.0], (B, 1))
+            init = torch.from_numpy(mpcqp.pack_plant_init(pos, np.tile([1.0, 0, 0, 0], (B, 1)),
+                                                          np.tile(list(pp.default_joint_pos), (B, 1)))).cuda()
+
+        def step():
+            mpcqp.plant_step_device(pp, DT, tau.data_ptr(), B, slot.data_ptr(), init.data_ptr() if init is not None else 0,
+                                    rows["sn"].data_ptr(), rows["pl"].data_ptr(), rows["st"].data_ptr(),
+                                    rows["tq"].data_ptr(), rows["po"].data_ptr(), stream)
+
+        step()  # initialise
+        torch.cuda.synchronize()
+        if stance:  # tau = J^T (-(0, 0, m g / 4)) at identity attitude, held for the 23 timed ticks
+            J = rows["tq"][:, _lib.TQ_JFOOT:_lib.TQ_JFOOT + 36].reshape(B, 4, 3, 3)
+            tau.copy_((-J[:, :, 2, :] * (pp.mass * pp.gravity / 4.0)).reshape(B, 12))
+        ms = median_ms(step)
+        po = rows["po"].cpu().numpy()
+        assert np.all(po[:, _lib.PT_STATUS] == 0.0)
+        assert np.all(po[:, _lib.PT_CONTACTS:_lib.PT_CONTACTS + 4] == (1.0 if stance else 0.0))
+        return ms
+
+    out["plant_kernel_substeps1_ms"] = plant_alone(1, True)
+    out["plant_kernel_substeps4_ms"] = plant_alone(4, True)
+    out["plant_kernel_swing_substeps4_ms"] = plant_alone(4, False)
+
+    # ---- the two neighbours it shares its thread mapping with ----
+    J, fkin, contacts, f_grf = torque_inputs(B, 1)
+    tq = torch.from_numpy(mpcqp.assemble_torque_records(J, fkin, contacts)).cuda()
+    res = np.zeros(B, dtype=mpcqp.RESULT_DTYPE)
+    res["f_body"] = f_grf
+    d_res = torch.from_numpy(res.view(np.float64).reshape(B, -1).copy()).cuda()
+    counter = torch.full((B,), 100, dtype=torch.int32, device="cuda")
+    tau = torch.zeros((B, 12), **f64)
+    out["torque_kernel_ms"] = median_ms(
+        lambda: mpcqp.joint_torques_device(tq.data_ptr(), d_res.data_ptr(), B, counter.data_ptr(), tau.data_ptr(), stream))
+    plp = mpcqp.default_plan_params()
+    st0 = torch.from_numpy(mpcqp.pack_states(mpcqp.synthetic_go1(B, seed=3, gait="stance"))).cuda()
+    pin = torch.from_numpy(mpcqp.pack_plan_inputs(np.tile(np.eye(3), (B, 1, 1)), np.full((B, 4), 30.0), 1)).cuda()
+    pslot = torch.zeros((B, mpcqp.plan_state_size()), **f64)
+    pout = torch.zeros((B, _lib.PO_SIZE), **f64)
+    out["plan_kernel_ms"] = median_ms(
+        lambda: mpcqp.leg_plan_device(plp, plp.control_dt, st0.data_ptr(), pin.data_ptr(), B, pslot.data_ptr(),
+                                      tq.data_ptr(), pout.data_ptr(), stream))
+
+    # ---- the graph-replayed tick with and without the stage ----
+    def pair(full):
+        kw = dict(plan=mpcqp.default_plan_params(), estimator=mpcqp.default_estimator_params(),
+                  command=mpcqp.default_command_params()) if full else {}
+        init, e = start_rows(B, [0.0, 0.8, -1.6], 0.05, 2)
+        k = ControlTick(B, dt=DT, plant=mpcqp.default_plant_params(), plant_init=init, **kw)
+        caller_rows(k, B, init[:, :3], e[:, 2], full)
+        k.prime_plant()
+        g_with = k.capture()
+        plant, k.plant = k.plant, None  # the same tick on the same buffers without its last stage
+        g_without = k.capture()
+        k.plant, k.graph = plant, g_with
+        for _ in range(12):  # past the torque map's zero-torque ticks
+            g_with.replay()
+        tensors = [v for v in vars(k).values() if isinstance(v, torch.Tensor)]
+        t_with, t_without, diff = [], [], []
+        for _ in range(T):
+            snap = [t.clone() for t in tensors]
+            t_without.append(event_ms(g_without.replay))
+            for t, c in zip(tensors, snap):
+                t.copy_(c)
+            t_with.append(event_ms(g_with.replay))
+            diff.append(t_with[-1] - t_without[-1])
+        k.close()
+        d = sorted(diff[WARMUP:])
+        return spread(t_with), spread(t_without), {"median_ms": d[len(d) // 2], "min_ms": d[0], "max_ms": d[-1]}
+
+    for name, full in (("mpc", False), ("full", True)):
+        w, wo, d = pair(full)
+        out[f"tick_graph_{name}_plant"], out[f"tick_graph_{name}"], out[f"tick_graph_{name}_paired_diff"] = w, wo, d
+        out[f"plant_share_of_{name}_tick"] = d["median_ms"] / wo["median_ms"]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
