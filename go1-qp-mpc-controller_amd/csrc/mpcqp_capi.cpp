@@ -892,6 +892,50 @@ int32_t mpcqp_plant_step_device(const mpcqp_plant_params* pp, double dt, const d
              : MPCQP_ERR_HIP;
 }
 
+void mpcqp_episode_default_params(mpcqp_episode_params* p) {
+  if (!p) return;
+  p->dt = 0.0025;
+  p->tilt_max = 0.5;
+  p->height_min = 0.12;
+  p->height_max = 0.6;
+  p->seed[0] = 0u;
+  p->seed[1] = 0u;
+  p->max_ticks = 2000;
+  p->pool_count = 0;
+  p->script_count = 0;
+  p->script_segments = 0;
+  p->log_len = 4;
+  p->pad_ = 0;
+}
+
+int32_t mpcqp_episode_params_size(void) { return (int32_t)sizeof(mpcqp_episode_params); }
+
+int32_t mpcqp_episode_buffers_size(void) { return (int32_t)sizeof(mpcqp_episode_buffers); }
+
+int32_t mpcqp_episode_state_size(void) { return MPCQP_ES_SIZE; }
+
+int32_t mpcqp_episode_device(const mpcqp_episode_params* ep, const mpcqp_episode_buffers* buf, int32_t batch,
+                             double* d_episode_state, void* stream) {
+  if (!ep || !buf || batch < 0) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  if (!d_episode_state || !buf->d_plant_out || !buf->d_plant_state) return MPCQP_ERR_INVALID_ARG;
+  if (!(ep->dt > 0.0) || !isfinite(ep->dt) || ep->max_ticks < 1 || ep->pool_count < 0) return MPCQP_ERR_INVALID_ARG;
+  if (buf->d_scripts && (ep->script_count < 1 || ep->script_segments < 1)) return MPCQP_ERR_INVALID_ARG;
+  if (buf->d_log && ep->log_len < 1) return MPCQP_ERR_INVALID_ARG;
+  if (buf->est_state_size < 0 || buf->plan_state_size < 0 || buf->cmd_state_size < 0 || buf->policy_state_size < 0 ||
+      buf->warm_size < 0)
+    return MPCQP_ERR_INVALID_ARG;
+  // the rows are cleared with 16-byte stores
+  const void* ptrs[] = {d_episode_state,     buf->d_plant_out,  buf->d_plant_state, buf->d_plant_init,
+                        buf->d_joint_torques, buf->d_sensors,    buf->d_cmd,         buf->d_results,
+                        buf->d_pool,          buf->d_scripts,    buf->d_states,
+                        buf->d_log,         buf->d_totals,     buf->d_est_state,   buf->d_plan_state,
+                        buf->d_cmd_state,     buf->d_policy_state, buf->d_warm};
+  for (const void* p : ptrs)
+    if ((reinterpret_cast<uintptr_t>(p) & 15u) != 0) return MPCQP_ERR_INVALID_ARG;
+  return mpcqp::launch_episode(*ep, *buf, batch, d_episode_state, stream) == hipSuccess ? MPCQP_OK : MPCQP_ERR_HIP;
+}
+
 void mpcqp_balance_default_params(mpcqp_balance_params* p) {
   if (!p) return;
   const double q[6] = {1.0, 1.0, 1.0, 400.0, 400.0, 100.0};  // A1RobotControl.cpp:11

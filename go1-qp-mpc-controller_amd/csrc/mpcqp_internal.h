@@ -136,6 +136,10 @@ hipError_t launch_plant(const mpcqp_plant_params& pp, double dt, const double* t
                         const double* init, double* sensors, double* plan_in, double* states, double* tq,
                         double* out, void* stream);
 
+// Episode stage: metrics, episode ends, log and on-device restarts (mpcqp_episode.hip)
+hipError_t launch_episode(const mpcqp_episode_params& ep, const mpcqp_episode_buffers& bf, int batch, double* slots,
+                          void* stream);
+
 // Policy stage: the Go1 RL controller and its servo stand (mpcqp_policy.hip).  The device-resident
 // description of one policy: the parameters (read with vector loads at a lane's joint index) and, per layer,
 // the input width, the output width padded to a multiple of 32, and the float offsets of its packed weights and

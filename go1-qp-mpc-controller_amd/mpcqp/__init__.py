@@ -9,6 +9,9 @@ from ._lib import (assemble_records_device, EXPORTED, LIB_PATH, RESULT_DTYPE, Mp
 from .balance import assemble_balance, assemble_balance_device, default_balance_gains, default_balance_params
 from .command import (CMD_STATE_DTYPE, CommandParams, command_device, command_state_size, default_command_params,
                       pack_commands)
+from .episode import (EPISODE_LOG_DTYPE, EPISODE_STATE_DTYPE, EPISODE_TOTALS_DTYPE, EpisodeBuffers, EpisodeParams,
+                      default_episode_params, episode_buffers, episode_device, episode_state_size,
+                      pack_episode_pool, pack_episode_scripts)
 from .estimator import (EST_OUT_DTYPE, EstimatorParams, default_estimator_params, estimator_state_size,
                         pack_estimator_slot, pack_sensors, state_estimate_device, unpack_estimator_slot)
 from .legplan import (PLAN_OUT_DTYPE, PlanParams, default_plan_params, leg_plan_device, leg_plan_typed_device,
@@ -38,4 +41,7 @@ __all__ = [
     "load_policy_weights", "policy_device", "policy_state_size",
     "PLANT_OUT_DTYPE", "PLANT_STATE_DTYPE", "PlantParams", "default_plant_params", "pack_plant_init",
     "plant_state_size", "plant_step_device",
+    "EPISODE_LOG_DTYPE", "EPISODE_STATE_DTYPE", "EPISODE_TOTALS_DTYPE", "EpisodeBuffers", "EpisodeParams",
+    "default_episode_params", "episode_buffers", "episode_device", "episode_state_size", "pack_episode_pool",
+    "pack_episode_scripts",
 ]

@@ -164,6 +164,25 @@ class PlantParams(ctypes.Structure):
     ]
 
 
+class EpisodeParams(ctypes.Structure):
+    """mpcqp_episode_params."""
+    _fields_ = [
+        ("dt", ctypes.c_double), ("tilt_max", ctypes.c_double), ("height_min", ctypes.c_double),
+        ("height_max", ctypes.c_double), ("seed", ctypes.c_uint32 * 2), ("max_ticks", ctypes.c_int32),
+        ("pool_count", ctypes.c_int32), ("script_count", ctypes.c_int32), ("script_segments", ctypes.c_int32),
+        ("log_len", ctypes.c_int32), ("pad_", ctypes.c_int32),
+    ]
+
+
+class EpisodeBuffers(ctypes.Structure):
+    """mpcqp_episode_buffers."""
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "d_plant_out", "d_plant_state", "d_plant_init", "d_joint_torques", "d_sensors", "d_cmd", "d_results", "d_pool",
+        "d_scripts", "d_states", "d_counter", "d_log", "d_totals", "d_est_state", "d_plan_state", "d_cmd_state",
+        "d_policy_state", "d_warm")] + [(name, ctypes.c_int32) for name in (
+            "est_state_size", "plan_state_size", "cmd_state_size", "policy_state_size", "warm_size", "pad_")]
+
+
 class Result(ctypes.Structure):
     """mpcqp_result."""
     _fields_ = [
@@ -204,6 +223,8 @@ EXPORTED = [
     "mpcqp_policy_default_params", "mpcqp_policy_params_size", "mpcqp_policy_create", "mpcqp_policy_destroy",
     "mpcqp_policy_state_size", "mpcqp_policy_device",
     "mpcqp_plant_default_params", "mpcqp_plant_params_size", "mpcqp_plant_state_size", "mpcqp_plant_step_device",
+    "mpcqp_episode_default_params", "mpcqp_episode_params_size", "mpcqp_episode_buffers_size",
+    "mpcqp_episode_state_size", "mpcqp_episode_device",
 ]
 
 _libs = {}
@@ -352,6 +373,19 @@ def load(debug=False):
         if L.mpcqp_plant_params_size() != ctypes.sizeof(PlantParams):
             raise MpcQpError(f"ABI mismatch: mpcqp_plant_params is {L.mpcqp_plant_params_size()} bytes in C, "
                              f"{ctypes.sizeof(PlantParams)} in ctypes")
+    if hasattr(L, "mpcqp_episode_device"):  # (absent from an older library given by MPCQP_LIB for an A/B)
+        L.mpcqp_episode_default_params.argtypes = [ctypes.POINTER(EpisodeParams)]
+        L.mpcqp_episode_default_params.restype = None
+        for name in ("mpcqp_episode_params_size", "mpcqp_episode_buffers_size", "mpcqp_episode_state_size"):
+            getattr(L, name).argtypes = []
+            getattr(L, name).restype = i32
+        L.mpcqp_episode_device.argtypes = [ctypes.POINTER(EpisodeParams), ctypes.POINTER(EpisodeBuffers), i32, vp, vp]
+        L.mpcqp_episode_device.restype = i32
+        if (L.mpcqp_episode_params_size() != ctypes.sizeof(EpisodeParams) or
+                L.mpcqp_episode_buffers_size() != ctypes.sizeof(EpisodeBuffers)):
+            raise MpcQpError(f"ABI mismatch: mpcqp_episode_params / _buffers are {L.mpcqp_episode_params_size()} / "
+                             f"{L.mpcqp_episode_buffers_size()} bytes in C, {ctypes.sizeof(EpisodeParams)} / "
+                             f"{ctypes.sizeof(EpisodeBuffers)} in ctypes")
     if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
         raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
                          f"{ctypes.sizeof(EstimatorParams)} in ctypes")

@@ -7,7 +7,8 @@ joint-space swing legs, flat ground, semi-implicit Euler in ``substeps`` substep
 swing legs' reaction on the trunk, foot slip, terrain, joint limits, and impact dynamics beyond zeroing the
 landing foot's velocity.  The state lives in a per-robot device slot of ``plant_state_size()`` doubles;
 zero-filled = fresh, and zeroing a robot's slots is how a fleet resets a fallen robot (a robot whose status
-is not 0 is frozen until then).
+is not 0 is frozen until then).  The episode stage (episode.py) does that on the device: it ends a fallen
+robot's episode, zeroes its slots over two ticks and restarts it from a drawn start row.
 """
 import ctypes
 

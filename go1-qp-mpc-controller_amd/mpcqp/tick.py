@@ -41,10 +41,17 @@ rigid-body model (single trunk, massless stance legs, joint-space swing legs, fl
 one control period on under the final ``torques`` row and writes the next tick's ``sensors`` and foot forces,
 so T replays are a T-tick closed-loop rollout with no host write in between.  Without ``estimator`` it also
 writes the ground truth of the estimator's fields into ``states`` / ``plan_in`` / ``tq_records``.
+
+With ``episode`` (an EpisodeParams; needs ``plant``) the tick ends with the episode stage: per robot it accumulates
+the episode's metrics, ends the episode on a plant status, the envelope or the time-out, writes it into
+``episode_log`` / ``episode_totals`` and restarts the robot over two ticks from a row of ``episode_pool`` drawn on
+the device, under one of ``episode_scripts``, so T replays are a Monte-Carlo evaluation of the fleet.
 """
 from . import _lib
 from .balance import assemble_balance_device, default_balance_gains
 from .command import command_device, command_state_size
+from .episode import (EL_SIZE, ET_SIZE, POOL_INIT, POOL_SIZE, SEG_SIZE, EpisodeParams, episode_buffers, episode_device,
+                      episode_state_size)
 from .estimator import estimator_state_size, state_estimate_device
 from .legplan import leg_plan_device, leg_plan_typed_device, plan_state_size
 from .plant import plant_state_size, plant_step_device
@@ -55,7 +62,8 @@ from .torques import joint_torques_device
 
 class ControlTick:
     def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None, command=None,
-                 control_type=None, balance=None, gains=None, policy=None, plant=None, plant_init=None):
+                 control_type=None, balance=None, gains=None, policy=None, plant=None, plant_init=None,
+                 episode=None, episode_pool=None, episode_scripts=None, episode_log_len=4):
         """control_type: None = the MPC-only tick; 0 / 1 = every robot takes the balance / the MPC branch;
         2 (with ``policy``) = every robot takes the policy branch;
         "per_robot" = the tick owns ``self.control_type``, an int32 [B] device tensor the caller writes
@@ -68,7 +76,14 @@ class ControlTick:
         ``plant`` (a PlantParams): the tick ends with the plant stage and owns ``plant_state``, ``plant_out`` and
         ``plant_init`` (from the rows ``plant_init`` [B, PI_SIZE], or None: the default stance); the caller then
         writes commands and desired values only.  Zeroing a robot's rows of ``plant_state`` and of the
-        controller's slots resets it."""
+        controller's slots resets it.
+        ``episode`` (an EpisodeParams; needs ``plant`` and ``episode_pool``, rows [P, POOL_SIZE] of
+        pack_episode_pool): the tick ends with the episode stage and owns ``episode_state``, ``episode_log``
+        [B, episode_log_len, EL_SIZE], ``episode_totals``, ``episode_pool``, ``episode_scripts`` (from
+        pack_episode_scripts, or None) and ``plant_init`` (pool row 0 until the first draw, unless ``plant_init``
+        is given).  Every robot starts fresh, so neither ``plant_init`` nor ``prime_plant()`` is needed: tick 1
+        draws, tick 2 primes, tick 3 is episode tick 0.  The counts, ``dt`` and ``log_len`` of the params are
+        set by the tick."""
         import torch
         self.torch = torch
         self.B = int(batch)
@@ -144,10 +159,40 @@ class ControlTick:
             if plant_init is not None:
                 rows = torch.as_tensor(plant_init, dtype=torch.float64).reshape(self.B, _lib.PI_SIZE)
                 self.plant_init = rows.to(dev).contiguous()
+        self.episode = None
+        if episode is not None:
+            if plant is None or episode_pool is None:
+                raise ValueError("ControlTick(episode=...) needs plant= and episode_pool=")
+            pool = torch.as_tensor(episode_pool, dtype=torch.float64).reshape(-1, POOL_SIZE)
+            ep = EpisodeParams.from_buffer_copy(episode)
+            ep.dt, ep.pool_count, ep.log_len = self.dt, pool.shape[0], int(episode_log_len)
+            ep.script_count = ep.script_segments = 0
+            self.episode_pool = pool.to(dev).contiguous()
+            self.episode_scripts = None
+            if episode_scripts is not None:
+                sc = torch.as_tensor(episode_scripts, dtype=torch.float64)
+                sc = sc.reshape(sc.shape[0], -1, SEG_SIZE)
+                ep.script_count, ep.script_segments = sc.shape[0], sc.shape[1]
+                self.episode_scripts = sc.to(dev).contiguous()
+            if self.plant_init is None:
+                self.plant_init = self.episode_pool[:1, POOL_INIT:POOL_INIT + _lib.PI_SIZE].repeat(self.B, 1)
+            self.episode_state = torch.zeros((self.B, episode_state_size()), **f64)  # zero = fresh
+            self.episode_log = torch.zeros((self.B, ep.log_len, EL_SIZE), **f64)
+            self.episode_totals = torch.zeros((self.B, ET_SIZE), **f64)
+            ptr = lambda name: getattr(self, name).data_ptr() if getattr(self, name, None) is not None else 0
+            size = lambda name: getattr(self, name).shape[1] if hasattr(self, name) else 0
+            self.episode_buffers = episode_buffers(
+                ptr("plant_out"), ptr("plant_state"), ptr("plant_init"), ptr("torques"), ptr("sensors"), ptr("cmd"),
+                ptr("results"), ptr("episode_pool"), ptr("episode_scripts"), ptr("states"), ptr("counter"),
+                ptr("episode_log"), ptr("episode_totals"), ptr("est_state"), size("est_state"), ptr("plan_state"),
+                size("plan_state"), ptr("cmd_state"), size("cmd_state"), ptr("policy_state"), size("policy_state"),
+                ptr("warm"), size("warm"))
+            self.episode = ep
         self.graph = None
 
-    def step(self, stream=None):
-        """Enqueue one tick on `stream` (default: torch's current stream)."""
+    def step(self, stream=None, episode=True):
+        """Enqueue one tick on `stream` (default: torch's current stream).  ``episode=False`` leaves the episode
+        stage out, for a caller that reads the tick's rows before enqueueing it with ``episode_stage()``."""
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
         if self.command is not None:
             command_device(self.command, self.dt, self.cmd.data_ptr(), self.states.data_ptr(),
@@ -157,7 +202,7 @@ class ControlTick:
                                   self.states.data_ptr(), self.B, self.est_state.data_ptr(),
                                   self.tq_records.data_ptr(), self.est_out.data_ptr(), s)
         if self.typed:
-            return self._step_typed(s)
+            return self._step_typed(s, episode)
         if self.plan is not None:
             leg_plan_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
                             self.plan_state.data_ptr(), self.tq_records.data_ptr(), self.plan_out.data_ptr(), s)
@@ -168,6 +213,14 @@ class ControlTick:
                              self.torques.data_ptr(), s)
         if self.plant is not None:
             self._step_plant(s)
+        if self.episode is not None and episode:
+            self.episode_stage(s)
+
+    def episode_stage(self, stream=None):
+        """Enqueue the episode stage alone: last in the tick, on whichever of the sensors, cmd and slot buffers
+        the tick has (``episode_buffers``)."""
+        s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        episode_device(self.episode, self.episode_buffers, self.B, self.episode_state.data_ptr(), s)
 
     def _step_plant(self, s):
         """The plant stage, last in the tick: the final ``torques`` row moves every robot one control period on.
@@ -187,7 +240,7 @@ class ControlTick:
         more step under the current ``torques``.)"""
         self._step_plant(stream if stream is not None else self.torch.cuda.current_stream().cuda_stream)
 
-    def _step_typed(self, s):
+    def _step_typed(self, s, episode=True):
         """plan -> both assemblies -> balance solve of the type-0 robots -> warm MPC solve of the type-1
         robots -> torque map -> policy stage of the type-2 robots; every kernel reads ``control_type`` when it
         runs."""
@@ -212,6 +265,8 @@ class ControlTick:
                           self.policy_out.data_ptr(), ty, 2, s)
         if self.plant is not None:
             self._step_plant(s)
+        if self.episode is not None and episode:
+            self.episode_stage(s)
 
     def capture(self):
         """Record step() as a graph.  Estimator, plan and warm slots, counters and torques keep evolving on replay,

@@ -684,7 +684,8 @@ int32_t mpcqp_plant_params_size(void); /* sizeof(mpcqp_plant_params), for bindin
 /* Plant slot, a caller-owned DEVICE buffer d_plant_state [batch][mpcqp_plant_state_size()] that must follow
  * its robot from tick to tick (offsets in doubles; FL FR RL RR leg order).  Zero-filled = fresh, the
  * convention of every other slot: the first tick initialises it and does not integrate.  Zeroing a robot's
- * slots (this one and the controller's) is how a fleet resets a fallen robot.                             */
+ * slots (this one and the controller's) is how a fleet resets a fallen robot; mpcqp_episode_device (below)
+ * does that on the device, in the two ticks a restart needs.                                              */
 #define MPCQP_PN_INIT 0        /* 0.0: fresh                                                             */
 #define MPCQP_PN_POS 1         /* [3] trunk position, world                                              */
 #define MPCQP_PN_QUAT 4        /* [4] trunk attitude as w, x, y, z                                       */
@@ -744,6 +745,157 @@ int32_t mpcqp_plant_step_device(const mpcqp_plant_params* pp, double dt, const d
                                 int32_t batch, double* d_plant_state, const double* d_plant_init,
                                 double* d_sensors, double* d_plan_in, double* d_states, double* d_tq_records,
                                 double* d_plant_out, void* stream);
+
+/* ---- episode stage: the last stage of a tick that ends with the plant.  Per robot it accumulates the
+ * episode's metrics from the tick's rows, decides when the episode ends, writes the episode into a per-robot
+ * log ring and per-robot totals, and restarts the robot from a start state drawn on the device out of a
+ * caller-built pool, under a command script that restarts with it.  T replays of a tick that ends with it are
+ * a Monte-Carlo evaluation of the fleet with no host write in between.
+ *
+ * A robot's phase (MPCQP_ES_PHASE) is 0 fresh, 1 running or 2 priming.  A restart takes two ticks, because a
+ * fresh plant slot initialises at the END of its tick: the controller stages of that tick still run on the
+ * fallen robot's stale rows and initialise their slots from them.
+ *   ending tick (phase 0 or 1).  A running robot first adds this tick to its metrics, then tests the end
+ *     reasons in the order of MPCQP_EP_END_*.  A fresh robot ends at once with reason 0 and writes no log row
+ *     (so a tick built with the stage needs no init rows and no separate plant launch).  On an end of a running
+ *     robot the stage writes the log row at ring position episode % log_len, adds the episode to the totals
+ *     and increments the episode index; on every end it counts the reason in the totals, draws the next
+ *     episode's pool and script indices, zero-fills the robot's plant slot row and torque row (the plant's
+ *     non-finite-torque rule must not block the initialisation), writes the pool row's init part to
+ *     d_plant_init and sets phase 2.
+ *   priming tick (phase 2), the next one: its plant stage has just initialised the fresh slot and written
+ *     clean sensor rows.  The stage zero-fills the robot's row of every controller slot given, of d_results and
+ *     of d_counter, writes MPCQP_ST_EULER_D / MPCQP_ST_POS_D from the pool row and, if an estimator slot is
+ *     given, zero into MPCQP_ST_POS / _LIN_VEL (the estimator's first tick leaves them as they are; zero is
+ *     A1CtrlStates::reset, A1CtrlStates.h:62-67), writes script segment 0 into the cmd row if its start tick is 0, takes the start pose from d_plant_out, clears the sums, sets tick 0 and
+ *     phase 1.  No tick is added to the metrics.
+ * Whatever the controller stages wrote between the two from stale rows is zeroed or rewritten by the priming
+ * tick.  A running robot that does not end and whose next script segment starts at tick + 1 gets that segment
+ * written to its cmd row (the stage runs last: it writes the next tick's command), then tick += 1.  A script
+ * should start with a segment at tick 0: otherwise the cmd row keeps the previous episode's last command until
+ * the first segment.
+ *
+ * Draws: Philox4x32-10 with key = seed[0], seed[1] and counter = (robot, episode index, 0, 0); pool index =
+ * (uint64(w0) * pool_count) >> 32, script index = (uint64(w1) * script_count) >> 32.  Integers only.
+ *
+ * Metrics: binary64, multiplies and adds not contracted, no libm call, in the statement order of
+ * tests/episode_reference.py; sums over the four legs are (l0 + l1) + (l2 + l3); a NaN metric is stored as the
+ * quiet NaN 0x7FF8000000000000, so the rows are bitwise those of the restatement.  No atomics: the totals are
+ * per-robot rows the host sums, so no number depends on scheduling.                                        */
+typedef struct mpcqp_episode_params {
+  double dt;               /* control period: the energy is sum(power) * dt.  0.0025                       */
+  double tilt_max;         /* envelope: roll^2 + pitch^2 > tilt_max^2 ends the episode.  0.5                */
+  double height_min;       /* envelope: trunk z < height_min or > height_max ends it.  0.12, 0.6            */
+  double height_max;
+  uint32_t seed[2];        /* the Philox key                                                               */
+  int32_t max_ticks;       /* an episode of this many ticks ends with MPCQP_EP_END_TIMEOUT.  2000          */
+  int32_t pool_count;      /* rows of d_pool                                                               */
+  int32_t script_count;    /* scripts of d_scripts                                                         */
+  int32_t script_segments; /* segments per script                                                          */
+  int32_t log_len;         /* rows per robot of the d_log ring.  4                                         */
+  int32_t pad_;
+} mpcqp_episode_params;
+
+void mpcqp_episode_default_params(mpcqp_episode_params* p);
+int32_t mpcqp_episode_params_size(void); /* sizeof(mpcqp_episode_params), for bindings */
+
+/* End reasons, in the order they are tested. */
+#define MPCQP_EP_END_FRESH 0       /* the slot was fresh: the first start                                  */
+#define MPCQP_EP_END_OUT_OF_REACH 1 /* MPCQP_PT_STATUS 1.0                                                 */
+#define MPCQP_EP_END_FALLEN 2      /* MPCQP_PT_STATUS 2.0                                                  */
+#define MPCQP_EP_END_BAD_TORQUE 3  /* MPCQP_PT_STATUS 3.0                                                  */
+#define MPCQP_EP_END_ENVELOPE 4    /* tilt, height, or a non-finite entry of MPCQP_PT_POS, _QUAT, _EULER   */
+#define MPCQP_EP_END_TIMEOUT 5     /* tick + 1 >= max_ticks                                                */
+#define MPCQP_EP_END_COUNT 6
+
+/* Pool row d_pool [pool_count][MPCQP_EP_POOL_SIZE]: a plant init row and the desired values that live in the
+ * caller's state row from tick to tick.  The host builds it, so no kinematics or trigonometry runs here.  */
+#define MPCQP_EP_POOL_INIT 0     /* [MPCQP_PI_SIZE] the plant init row                                     */
+#define MPCQP_EP_POOL_EULER_D 20 /* [3] root_euler_d                                                       */
+#define MPCQP_EP_POOL_POS_D 23   /* [3] root_pos_d                                                         */
+#define MPCQP_EP_POOL_SIZE 28    /* 26 used, padded to a multiple of 4 doubles                             */
+
+/* Script segment, d_scripts [script_count][script_segments][MPCQP_EP_SEG_SIZE], sorted by start tick; a start
+ * tick < 0 ends the list. */
+#define MPCQP_EP_SEG_TICK 0      /* the episode tick at which the segment takes effect                     */
+#define MPCQP_EP_SEG_CMD 1       /* [7] MPCQP_CM_VEL, MPCQP_CM_RATE, MPCQP_CM_MODE_REQUEST                 */
+#define MPCQP_EP_SEG_SIZE 8
+
+/* Episode slot d_episode_state [batch][mpcqp_episode_state_size()]; zero-filled = fresh. */
+#define MPCQP_ES_PHASE 0         /* 0.0 fresh, 1.0 running, 2.0 priming                                    */
+#define MPCQP_ES_TICK 1          /* ticks of the episode so far                                            */
+#define MPCQP_ES_EPISODE 2       /* index of the episode that runs (or is being primed)                    */
+#define MPCQP_ES_POOL 3          /* its pool row                                                           */
+#define MPCQP_ES_SCRIPT 4        /* its script                                                             */
+#define MPCQP_ES_SEG 5           /* the script's next segment                                              */
+#define MPCQP_ES_METRICS 6       /* [MPCQP_EM_SIZE] the metrics so far                                     */
+#define MPCQP_ES_SIZE 24         /* 23 used, padded to a multiple of 4 doubles                             */
+int32_t mpcqp_episode_state_size(void);
+
+/* The metrics block of the slot and of a log row. */
+#define MPCQP_EM_TILT2_MAX 0     /* max of roll^2 + pitch^2, the start included                            */
+#define MPCQP_EM_Z_MIN 1         /* min and max trunk z, the start included                                */
+#define MPCQP_EM_Z_MAX 2
+#define MPCQP_EM_ENERGY 3        /* sum over ticks of (sum_j tau_j qd_j) * dt                              */
+#define MPCQP_EM_TAU2 4          /* sum of tau_j^2                                                         */
+#define MPCQP_EM_ERR_V 5         /* [3] sum of squared body-frame tracking error: v_x, v_y, yaw rate       */
+#define MPCQP_EM_ITERS 8         /* sum of mpcqp_result.iters                                              */
+#define MPCQP_EM_NOT_SOLVED 9    /* ticks whose mpcqp_result.status is not MPCQP_STATUS_SOLVED             */
+#define MPCQP_EM_LOW_CONTACT 10  /* ticks with fewer than two contacts                                     */
+#define MPCQP_EM_START 11        /* [3] x, y, yaw at the start                                             */
+#define MPCQP_EM_END 14          /* [3] x, y, yaw at the last tick                                         */
+#define MPCQP_EM_SIZE 17
+
+/* Log row d_log [batch][log_len][MPCQP_EL_SIZE], the ring of a robot's last log_len episodes. */
+#define MPCQP_EL_EPISODE 0
+#define MPCQP_EL_POOL 1
+#define MPCQP_EL_SCRIPT 2
+#define MPCQP_EL_LENGTH 3        /* ticks                                                                  */
+#define MPCQP_EL_REASON 4        /* MPCQP_EP_END_*                                                         */
+#define MPCQP_EL_METRICS 5       /* [MPCQP_EM_SIZE]                                                        */
+#define MPCQP_EL_SIZE 24         /* 22 used, padded to a multiple of 4 doubles                             */
+
+/* Totals row d_totals [batch][MPCQP_ET_SIZE]; the host sums the rows. */
+#define MPCQP_ET_EPISODES 0      /* episodes completed (the fresh start is none)                           */
+#define MPCQP_ET_TICKS 1         /* their ticks                                                            */
+#define MPCQP_ET_REASON 2        /* [MPCQP_EP_END_COUNT] ends per reason                                   */
+#define MPCQP_ET_SIZE 8
+
+/* The stage's buffers: DEVICE pointers and the row sizes, in doubles, of the controller slots.  Every pointer
+ * except d_plant_out and d_plant_state may be NULL, which skips what it serves: without d_joint_torques the
+ * energy and the torque sum stay 0, without d_sensors the energy, without d_results the iteration and
+ * not-solved counts; without d_cmd the tracking error is taken against a zero command and no script is written.
+ * Every pointer of doubles must be 16-byte aligned (MPCQP_ERR_INVALID_ARG otherwise). */
+typedef struct mpcqp_episode_buffers {
+  const double* d_plant_out;  /* [batch][MPCQP_PT_SIZE]  read                                              */
+  double* d_plant_state;      /* [batch][MPCQP_PN_SIZE]  zero-filled on an end                             */
+  double* d_plant_init;       /* [batch][MPCQP_PI_SIZE]  written on an end                                 */
+  double* d_joint_torques;    /* [batch][12]             read; zero-filled on an end                       */
+  const double* d_sensors;    /* [batch][MPCQP_SN_SIZE]  MPCQP_SN_JOINT_VEL read, for the energy           */
+  double* d_cmd;              /* [batch][MPCQP_CM_SIZE]  read (tracking error); script segments written    */
+  mpcqp_result* d_results;    /* [batch]                 status and iters read; zero-filled when priming   */
+  const double* d_pool;       /* [pool_count][MPCQP_EP_POOL_SIZE]                                          */
+  const double* d_scripts;    /* [script_count][script_segments][MPCQP_EP_SEG_SIZE]                        */
+  double* d_states;           /* [batch][MPCQP_ST_SIZE]  MPCQP_ST_EULER_D, _POS_D written when priming      */
+  int32_t* d_counter;         /* [batch]                 the torque map's counter, zeroed when priming     */
+  double* d_log;              /* [batch][log_len][MPCQP_EL_SIZE]                                           */
+  double* d_totals;           /* [batch][MPCQP_ET_SIZE]                                                    */
+  double* d_est_state;        /* the controller slots, zero-filled when priming, with their row sizes      */
+  double* d_plan_state;
+  double* d_cmd_state;
+  double* d_policy_state;
+  double* d_warm;             /* row size mpcqp_warm_state_size(horizon); may be odd                       */
+  int32_t est_state_size, plan_state_size, cmd_state_size, policy_state_size, warm_size;
+  int32_t pad_;
+} mpcqp_episode_buffers;
+int32_t mpcqp_episode_buffers_size(void); /* sizeof(mpcqp_episode_buffers), for bindings */
+
+/* One episode tick for `batch` robots (DEVICE pointers, async on `stream`, no allocation and no
+ * synchronization: hipGraph-capture safe; one kernel).  Chain it last in the tick, after
+ * mpcqp_plant_step_device on the same stream, and give the plant stage the same d_plant_init.  The structs are
+ * read when the call is made. */
+int32_t mpcqp_episode_device(const mpcqp_episode_params* ep, const mpcqp_episode_buffers* buf, int32_t batch,
+                             double* d_episode_state, void* stream);
 
 const char* mpcqp_status_str(int32_t status);
 const char* mpcqp_error_str(int32_t err);

@@ -10,7 +10,18 @@ between, for three ticks, each under standing commands:
   servo_walk_gains   (not in the default list) the same with the walk mode's gains (20 / 50 / 50, 1 / 2 / 2) in
           place of the servo gains
 
-Per form: ticks/s over the timed replays (HIP events around chunks of replays; the host only reads between
+and, with the episode stage as the tick's last stage (ControlTick(episode=): on-device resets from a pool of start
+rows, a time-out, an envelope; not in the default list), four more:
+
+  mpc_ep     the mpc setup; every robot that leaves the standing envelope or times out is restarted on the device
+  full_ep    the full setup, likewise
+  full_walk  the full setup under a script that toggles walk mode and commands 0.3 m/s forward at episode tick 100
+  servo_ep   the servo setup: the fleet that sinks and falls, restarted and counted
+
+These report episodes completed, the end-reason histogram, ticks/s and medians of the logged episodes' metrics
+from the device's totals and log, read once after the last replay; they never rerun with a read per tick.
+
+Per form of the first kind: ticks/s over the timed replays (HIP events around chunks of replays; the host only reads between
 chunks), how many robots ended with a plant status != 0, and how many are out of a standing envelope (tilt >
 0.3 rad, or the trunk more than 5 cm from where standing should hold it).  If any robot went wrong the form is
 run once more with a read after every tick to find the first tick at which it did.
@@ -97,6 +108,121 @@ def make(form, B, seed):
     raise ValueError(form)
 
 
+def full_stance():
+    """(leg angles, trunk height) of the stance at the command stage's body height: both links at the same
+    angle to the vertical."""
+    pp = mpcqp.default_plant_params()
+    h = mpcqp.default_command_params().body_height_init
+    q1 = float(np.arccos(h / (2.0 * pp.rho_fix[3])))
+    return [0.0, q1, -2.0 * q1], h
+
+
+def episode_pool(P, q_leg, tilt, seed, height=None):
+    """P pool rows for the episode stage: start_rows, with root_pos_d = (0, 0, start height or `height`) and
+    root_euler_d = (0, 0, start yaw)."""
+    init, e = start_rows(P, q_leg, tilt, seed)
+    z = init[:, 2] if height is None else np.full(P, float(height))
+    zero = np.zeros(P)
+    return mpcqp.pack_episode_pool(init, np.stack([zero, zero, e[:, 2]], 1), np.stack([zero, zero, z], 1))
+
+
+EPISODE_FORMS = ("mpc_ep", "full_ep", "full_walk", "servo_ep")
+POOL, MAX_TICKS, WALK_AT, WALK_VX = 64, 500, 100, 0.3
+
+
+def make_episode(form, B, seed):
+    """The mpc / full setups with the episode stage: a pool of POOL start rows, a time-out of MAX_TICKS ticks and
+    the standing envelope of `look` (tilt 0.3 rad, 5 cm about the standing height).  full_walk: every episode's
+    script toggles walk mode and commands WALK_VX m/s forward at episode tick WALK_AT; its envelope keeps the
+    tilt bound and takes the height bounds of the stage's defaults."""
+    pp = mpcqp.default_plant_params()
+    extra = None
+    if form == "mpc_ep":
+        q, tilt = [0.0, 0.8, -1.6], 0.09
+        pool = episode_pool(POOL, q, tilt, seed)
+        stand = float(np.median(pool[:, 2]))
+        kw, comp = {}, False
+    elif form == "servo_ep":
+        ws, bs = seeded_weights(0)
+        extra = mpcqp.Policy(ws, bs, mpcqp.default_policy_params())
+        pool = episode_pool(POOL, [0.0, 0.8, -1.6], 0.0, seed)
+        stand_pos = np.array(mpcqp.default_policy_params().stand_pos).reshape(1, 4, 3)
+        rel = er.fk(stand_pos, np.array(pp.rho_opt).reshape(1, 4, 3), np.array(pp.rho_fix).reshape(1, 4, 5))
+        stand = float(-rel[0, :, 2].mean())
+        kw, comp = dict(control_type=2, policy=extra), True
+    else:
+        q, stand = full_stance()
+        pool = episode_pool(POOL, q, 0.05, seed, stand)
+        kw, comp = dict(plan=mpcqp.default_plan_params(), estimator=mpcqp.default_estimator_params(),
+                        command=mpcqp.default_command_params()), True
+    over = dict(height_min=stand - 0.05, height_max=stand + 0.05)
+    scripts = None
+    if form == "full_walk":
+        over = {}
+        scripts = mpcqp.pack_episode_scripts([[(0, (0, 0, 0), (0, 0, 0), False),
+                                               (WALK_AT, (WALK_VX, 0, 0), (0, 0, 0), True)]])
+    ep = mpcqp.default_episode_params(max_ticks=MAX_TICKS, tilt_max=0.3, seed=seed, **over)
+    k = ControlTick(B, dt=DT, plant=pp, episode=ep, episode_pool=pool, episode_scripts=scripts, episode_log_len=8,
+                    **kw)
+    caller_rows(k, B, np.zeros((B, 3)), np.zeros(B), comp)  # the constants; the stage writes the desired values
+    return k, extra
+
+
+def run_episode(form, B, T, seed):
+    """T replays of the tick that ends with the episode stage; everything reported comes from the totals and the
+    log rows, read once after the last replay."""
+    from mpcqp import episode as me
+    k, extra = make_episode(form, B, seed)
+    try:
+        k.capture()
+        torch.cuda.synchronize()
+        ms = 0.0
+        for t0 in range(0, T, CHUNK):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(min(CHUNK, T - t0)):
+                k.replay()
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms += ev[0].elapsed_time(ev[1])
+        tot = np.frombuffer(k.episode_totals.cpu().numpy().tobytes(), dtype=mpcqp.EPISODE_TOTALS_DTYPE)
+        log = np.frombuffer(k.episode_log.cpu().numpy().tobytes(), dtype=mpcqp.EPISODE_LOG_DTYPE)
+        es = np.frombuffer(k.episode_state.cpu().numpy().tobytes(), dtype=mpcqp.EPISODE_STATE_DTYPE)
+        log = log[log["length"] > 0]
+        r = {"form": form, "batch": B, "ticks": T, "dt": DT, "ticks_per_s": T / (ms * 1e-3),
+             "robot_ticks_per_s": B * T / (ms * 1e-3), "ms_per_tick": ms / T, "max_ticks": MAX_TICKS, "pool": POOL,
+             "episodes": int(tot["episodes"].sum()), "episode_ticks": int(tot["ticks"].sum()),
+             "end_reasons": {n: int(c) for n, c in zip(me.END_NAMES, tot["reason"].sum(0))},
+             "robots_running_at_the_end": int((es["phase"] == 1.0).sum()),
+             "logged_episodes": int(log.size)}
+        if log.size:
+            with np.errstate(invalid="ignore"):
+                r.update({"length_mean": float(log["length"].mean()), "length_median": float(np.median(log["length"])),
+                          "tilt_max_median": float(np.sqrt(np.nanmedian(log["tilt2_max"]))),
+                          "z_min_median": float(np.nanmedian(log["z_min"])),
+                          "energy_per_tick_median": float(np.nanmedian(log["energy"] / log["length"])),
+                          "err_vx_rms_median": float(np.sqrt(np.nanmedian(log["err_v"][:, 0] / log["length"]))),
+                          "not_solved_share": float(log["not_solved"].sum() / log["length"].sum()),
+                          "low_contact_share": float(log["low_contact"].sum() / log["length"].sum())})
+                if form == "full_walk":
+                    d = log["end"][:, :2] - log["start"][:, :2]
+                    yaw = log["start"][:, 2]
+                    fwd = d[:, 0] * np.cos(yaw) + d[:, 1] * np.sin(yaw)
+                    walked = log["length"] > WALK_AT
+                    r.update({"walk_at": WALK_AT, "walk_vx": WALK_VX, "episodes_that_reached_the_toggle": int(walked.sum()),
+                              "ticks_after_the_toggle_median": float(np.median(log["length"][walked] - WALK_AT))
+                              if walked.any() else None,
+                              "forward_m_median": float(np.nanmedian(fwd[walked])) if walked.any() else None,
+                              "forward_m_max": float(np.nanmax(fwd[walked])) if walked.any() else None,
+                              "end_reasons_after_the_toggle": {
+                                  n: int((log["reason"][walked] == i).sum()) for i, n in enumerate(me.END_NAMES)}})
+    finally:
+        k.close()
+        if extra is not None:
+            extra.close()
+    return r
+
+
 def look(k, stand_z):
     po = k.plant_out.cpu().numpy()
     tilt = np.hypot(po[:, _lib.PT_EULER], po[:, _lib.PT_EULER + 1])
@@ -171,9 +297,12 @@ def main():
     ap.add_argument("--ticks", type=int, default=2000)
     ap.add_argument("--forms", nargs="+", default=["mpc", "full", "servo"])
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--max-ticks", type=int, default=MAX_TICKS, help="time-out of the episode forms")
     a = ap.parse_args()
+    globals()["MAX_TICKS"] = a.max_ticks
     for form in a.forms:
-        print(json.dumps(run(form, a.batch, a.ticks, a.seed)), flush=True)
+        go = run_episode if form in EPISODE_FORMS else run
+        print(json.dumps(go(form, a.batch, a.ticks, a.seed)), flush=True)
 
 
 if __name__ == "__main__":
