@@ -892,6 +892,57 @@ int32_t mpcqp_plant_step_device(const mpcqp_plant_params* pp, double dt, const d
              : MPCQP_ERR_HIP;
 }
 
+int32_t mpcqp_plant_step_wrench_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                       const double* d_wrench, int32_t batch, double* d_plant_state,
+                                       const double* d_plant_init, double* d_sensors, double* d_plan_in,
+                                       double* d_states, double* d_tq_records, double* d_plant_out, void* stream) {
+  if (!pp || batch < 0 || !(dt > 0.0) || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
+  if (pp->substeps < 1 || pp->substeps > 16) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_joint_torques || !d_plant_state)) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_plant_wrench(*pp, dt, d_joint_torques, d_wrench, batch, d_plant_state, d_plant_init, d_sensors,
+                                    d_plan_in, d_states, d_tq_records, d_plant_out, stream) == hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
+void mpcqp_disturb_default_params(mpcqp_disturb_params* p) {
+  if (!p) return;
+  p->load_mass_max = 0.0;
+  p->gravity = 9.81;
+  p->bias_acc = 0.0;
+  p->bias_gyro = 0.0;
+  p->push_force[0] = p->push_force[1] = 0.0;
+  for (int k = 0; k < 3; ++k) p->load_point[k] = p->push_point[k] = 0.0;
+  for (int k = 0; k < 4; ++k) p->sigma[k] = 0.0;
+  p->seed[0] = 0u;
+  p->seed[1] = 0u;
+  p->push_start = 0;
+  p->push_interval = 0;
+  p->push_duration = 1;
+  p->dir_count = 0;
+}
+
+int32_t mpcqp_disturb_params_size(void) { return (int32_t)sizeof(mpcqp_disturb_params); }
+
+int32_t mpcqp_disturb_buffers_size(void) { return (int32_t)sizeof(mpcqp_disturb_buffers); }
+
+int32_t mpcqp_disturb_device(const mpcqp_disturb_params* dp, const mpcqp_disturb_buffers* buf, int32_t batch,
+                             void* stream) {
+  if (!dp || !buf || batch < 0) return MPCQP_ERR_INVALID_ARG;
+  if (dp->push_interval < 0) return MPCQP_ERR_INVALID_ARG;
+  if (dp->push_interval > 0) {
+    if (dp->push_duration < 1 || dp->push_duration > dp->push_interval || dp->push_start < 0)
+      return MPCQP_ERR_INVALID_ARG;
+    if (!buf->d_dirs || dp->dir_count < 1) return MPCQP_ERR_INVALID_ARG;
+  }
+  if (!buf->d_episode_state || !buf->d_wrench) return MPCQP_ERR_INVALID_ARG;
+  if ((buf->d_sensors == nullptr) != (buf->d_sensors_noisy == nullptr)) return MPCQP_ERR_INVALID_ARG;
+  if (buf->d_sensors && buf->d_sensors == buf->d_sensors_noisy) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_disturb(*dp, *buf, batch, stream) == hipSuccess ? MPCQP_OK : MPCQP_ERR_HIP;
+}
+
 void mpcqp_episode_default_params(mpcqp_episode_params* p) {
   if (!p) return;
   p->dt = 0.0025;

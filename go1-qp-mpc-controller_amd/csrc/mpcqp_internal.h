@@ -135,6 +135,13 @@ hipError_t launch_command(const mpcqp_command_params& cp, double dt, double* cmd
 hipError_t launch_plant(const mpcqp_plant_params& pp, double dt, const double* torques, int batch, double* slots,
                         const double* init, double* sensors, double* plan_in, double* states, double* tq,
                         double* out, void* stream);
+// the same with the external forces of a wrench row (wrench != nullptr), another instantiation of the kernel
+hipError_t launch_plant_wrench(const mpcqp_plant_params& pp, double dt, const double* torques, const double* wrench,
+                               int batch, double* slots, const double* init, double* sensors, double* plan_in,
+                               double* states, double* tq, double* out, void* stream);
+
+// Disturbance stage: pushes, payload weight, sensor noise and IMU biases drawn on the device (mpcqp_disturb.hip)
+hipError_t launch_disturb(const mpcqp_disturb_params& dp, const mpcqp_disturb_buffers& bf, int batch, void* stream);
 
 // Episode stage: metrics, episode ends, log and on-device restarts (mpcqp_episode.hip)
 hipError_t launch_episode(const mpcqp_episode_params& ep, const mpcqp_episode_buffers& bf, int batch, double* slots,

@@ -5,7 +5,8 @@
 // The model (include/mpcqp.h has the statement): a single rigid trunk, massless stance legs whose held
 // feet turn the joint torques into ground reactions f = -R J^-T tau (the inverse of mpcqp_torque.hip's
 // tau = J^T (-f_grf)), joint-space swing legs that exert nothing on the trunk, flat ground z = 0,
-// semi-implicit Euler in `substeps` substeps per tick.  A held foot does not slip.  Left out: leg mass,
+// semi-implicit Euler in `substeps` substeps per tick; optionally two external forces on the trunk (the wrench
+// row of mpcqp_plant_step_wrench_device).  A held foot does not slip.  Left out: leg mass,
 // the swing legs' reaction on the trunk, foot slip, terrain, joint limits, and impact dynamics beyond
 // zeroing the landing foot's velocity.  The joint inertias are the model's own choice, not identified
 // from a robot description.
@@ -173,12 +174,15 @@ __device__ __forceinline__ bool kinematics(const Leg& g, State& s, double (&R)[9
   return ok;
 }
 
+// WRENCH: the external forces of a wrench row act on the trunk (include/mpcqp.h has the statement).  Without it
+// the row is never read, and the instantiation is the kernel as it was before the wrench existed.
+template <bool WRENCH>
 __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp, const double dt,
                                                     const double* __restrict__ torques, const int batch,
                                                     double* __restrict__ slots, const double* __restrict__ init,
                                                     double* __restrict__ sensors, double* __restrict__ plan_in,
                                                     double* __restrict__ states, double* __restrict__ tq,
-                                                    double* __restrict__ out) {
+                                                    double* __restrict__ out, const double* __restrict__ wrench) {
 #pragma clang fp contract(off)
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = gid >> 2, leg = gid & 3;
@@ -191,7 +195,22 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
   double tau[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) tau[k] = torques[(size_t)12 * b + 3 * leg + k];
-  if (quad_any(!(__builtin_isfinite(tau[0]) && __builtin_isfinite(tau[1]) && __builtin_isfinite(tau[2])))) {
+  bool finite = __builtin_isfinite(tau[0]) && __builtin_isfinite(tau[1]) && __builtin_isfinite(tau[2]);
+  // the wrench row, alike on the four lanes: forces F0, F1 (world) at the points P0, P1 (body)
+  double F0[3] = {0.0, 0.0, 0.0}, P0[3] = {0.0, 0.0, 0.0}, F1[3] = {0.0, 0.0, 0.0}, P1[3] = {0.0, 0.0, 0.0};
+  if constexpr (WRENCH) {
+    const double* wr = wrench + (size_t)MPCQP_PW_SIZE * b;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      F0[k] = wr[MPCQP_PW_FORCE0 + k];
+      P0[k] = wr[MPCQP_PW_POINT0 + k];
+      F1[k] = wr[MPCQP_PW_FORCE1 + k];
+      P1[k] = wr[MPCQP_PW_POINT1 + k];
+      finite = finite && __builtin_isfinite(F0[k]) && __builtin_isfinite(P0[k]) && __builtin_isfinite(F1[k]) &&
+               __builtin_isfinite(P1[k]);
+    }
+  }
+  if (quad_any(!finite)) {
     if (o && leg == 0) o[MPCQP_PT_STATUS] = 3.0;
     return;
   }
@@ -314,6 +333,23 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
           M[k] = quad_sum(s.st ? m[k] : 0.0);
         }
       }
+      double ce[3] = {0.0, 0.0, 0.0};  // the external forces' moment, body frame
+      if constexpr (WRENCH) {
+        double fb0[3], fb1[3], c0[3], c1[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          // a zero term is skipped, not added: x + 0.0 would turn a sum of -0.0 into +0.0, and a zero row must
+          // leave every bit of the kernel without a wrench
+          const double fe = F0[k] + F1[k];
+          F[k] = fe == 0.0 ? F[k] : F[k] + fe;
+        }
+        mat_t_vec(R, F0, fb0);
+        mat_t_vec(R, F1, fb1);
+        cross(P0, fb0, c0);
+        cross(P1, fb1, c1);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ce[k] = c0[k] + c1[k];
+      }
       double a[3], wd[3];
       {
 #pragma unroll
@@ -324,6 +360,10 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
         for (int e = 0; e < 9; ++e) Ib[e] = pp.inertia[e];
         mat_vec(Ib, s.w, Iw);
         mat_t_vec(R, M, rm);
+        if constexpr (WRENCH) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) rm[k] = ce[k] == 0.0 ? rm[k] : rm[k] + ce[k];
+        }
         cross(s.w, Iw, wi);
 #pragma unroll
         for (int k = 0; k < 3; ++k) rhs[k] = rm[k] - wi[k];
@@ -511,8 +551,18 @@ hipError_t launch_plant(const mpcqp_plant_params& pp, double dt, const double* t
                         const double* init, double* sensors, double* plan_in, double* states, double* tq,
                         double* out, void* stream) {
   const int threads = 4 * batch;
-  hipLaunchKernelGGL(plant::plant_kernel, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, pp, dt,
-                     torques, batch, slots, init, sensors, plan_in, states, tq, out);
+  hipLaunchKernelGGL(plant::plant_kernel<false>, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, pp,
+                     dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, (const double*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_plant_wrench(const mpcqp_plant_params& pp, double dt, const double* torques, const double* wrench,
+                               int batch, double* slots, const double* init, double* sensors, double* plan_in,
+                               double* states, double* tq, double* out, void* stream) {
+  if (!wrench) return launch_plant(pp, dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, stream);
+  const int threads = 4 * batch;
+  hipLaunchKernelGGL(plant::plant_kernel<true>, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, pp,
+                     dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, wrench);
   return hipGetLastError();
 }
 

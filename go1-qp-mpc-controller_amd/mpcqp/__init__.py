@@ -9,6 +9,8 @@ from ._lib import (assemble_records_device, EXPORTED, LIB_PATH, RESULT_DTYPE, Mp
 from .balance import assemble_balance, assemble_balance_device, default_balance_gains, default_balance_params
 from .command import (CMD_STATE_DTYPE, CommandParams, command_device, command_state_size, default_command_params,
                       pack_commands)
+from .disturb import (DISTURB_OUT_DTYPE, DisturbBuffers, DisturbParams, default_disturb_params, disturb_buffers,
+                      disturb_device, disturbance_of, pack_push_dirs, plant_step_wrench_device)
 from .episode import (EPISODE_LOG_DTYPE, EPISODE_STATE_DTYPE, EPISODE_TOTALS_DTYPE, EpisodeBuffers, EpisodeParams,
                       default_episode_params, episode_buffers, episode_device, episode_state_size,
                       pack_episode_pool, pack_episode_scripts)
@@ -44,4 +46,6 @@ __all__ = [
     "EPISODE_LOG_DTYPE", "EPISODE_STATE_DTYPE", "EPISODE_TOTALS_DTYPE", "EpisodeBuffers", "EpisodeParams",
     "default_episode_params", "episode_buffers", "episode_device", "episode_state_size", "pack_episode_pool",
     "pack_episode_scripts",
+    "DISTURB_OUT_DTYPE", "DisturbBuffers", "DisturbParams", "default_disturb_params", "disturb_buffers",
+    "disturb_device", "disturbance_of", "pack_push_dirs", "plant_step_wrench_device",
 ]

@@ -183,6 +183,23 @@ class EpisodeBuffers(ctypes.Structure):
             "est_state_size", "plan_state_size", "cmd_state_size", "policy_state_size", "warm_size", "pad_")]
 
 
+class DisturbParams(ctypes.Structure):
+    """mpcqp_disturb_params."""
+    _fields_ = [
+        ("load_mass_max", ctypes.c_double), ("gravity", ctypes.c_double), ("load_point", ctypes.c_double * 3),
+        ("bias_acc", ctypes.c_double), ("bias_gyro", ctypes.c_double), ("push_force", ctypes.c_double * 2),
+        ("push_point", ctypes.c_double * 3), ("sigma", ctypes.c_double * 4), ("seed", ctypes.c_uint32 * 2),
+        ("push_start", ctypes.c_int32), ("push_interval", ctypes.c_int32), ("push_duration", ctypes.c_int32),
+        ("dir_count", ctypes.c_int32),
+    ]
+
+
+class DisturbBuffers(ctypes.Structure):
+    """mpcqp_disturb_buffers."""
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "d_episode_state", "d_wrench", "d_sensors", "d_sensors_noisy", "d_dirs", "d_disturb_out")]
+
+
 class Result(ctypes.Structure):
     """mpcqp_result."""
     _fields_ = [
@@ -225,6 +242,8 @@ EXPORTED = [
     "mpcqp_plant_default_params", "mpcqp_plant_params_size", "mpcqp_plant_state_size", "mpcqp_plant_step_device",
     "mpcqp_episode_default_params", "mpcqp_episode_params_size", "mpcqp_episode_buffers_size",
     "mpcqp_episode_state_size", "mpcqp_episode_device",
+    "mpcqp_plant_step_wrench_device", "mpcqp_disturb_default_params", "mpcqp_disturb_params_size",
+    "mpcqp_disturb_buffers_size", "mpcqp_disturb_device",
 ]
 
 _libs = {}
@@ -386,6 +405,22 @@ def load(debug=False):
             raise MpcQpError(f"ABI mismatch: mpcqp_episode_params / _buffers are {L.mpcqp_episode_params_size()} / "
                              f"{L.mpcqp_episode_buffers_size()} bytes in C, {ctypes.sizeof(EpisodeParams)} / "
                              f"{ctypes.sizeof(EpisodeBuffers)} in ctypes")
+    if hasattr(L, "mpcqp_disturb_device"):  # (absent from an older library given by MPCQP_LIB for an A/B)
+        L.mpcqp_plant_step_wrench_device.argtypes = [ctypes.POINTER(PlantParams), ctypes.c_double, vp, vp, i32, vp, vp,
+                                                     vp, vp, vp, vp, vp, vp]
+        L.mpcqp_plant_step_wrench_device.restype = i32
+        L.mpcqp_disturb_default_params.argtypes = [ctypes.POINTER(DisturbParams)]
+        L.mpcqp_disturb_default_params.restype = None
+        for name in ("mpcqp_disturb_params_size", "mpcqp_disturb_buffers_size"):
+            getattr(L, name).argtypes = []
+            getattr(L, name).restype = i32
+        L.mpcqp_disturb_device.argtypes = [ctypes.POINTER(DisturbParams), ctypes.POINTER(DisturbBuffers), i32, vp]
+        L.mpcqp_disturb_device.restype = i32
+        if (L.mpcqp_disturb_params_size() != ctypes.sizeof(DisturbParams) or
+                L.mpcqp_disturb_buffers_size() != ctypes.sizeof(DisturbBuffers)):
+            raise MpcQpError(f"ABI mismatch: mpcqp_disturb_params / _buffers are {L.mpcqp_disturb_params_size()} / "
+                             f"{L.mpcqp_disturb_buffers_size()} bytes in C, {ctypes.sizeof(DisturbParams)} / "
+                             f"{ctypes.sizeof(DisturbBuffers)} in ctypes")
     if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
         raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
                          f"{ctypes.sizeof(EstimatorParams)} in ctypes")

@@ -46,10 +46,17 @@ With ``episode`` (an EpisodeParams; needs ``plant``) the tick ends with the epis
 the episode's metrics, ends the episode on a plant status, the envelope or the time-out, writes it into
 ``episode_log`` / ``episode_totals`` and restarts the robot over two ticks from a row of ``episode_pool`` drawn on
 the device, under one of ``episode_scripts``, so T replays are a Monte-Carlo evaluation of the fleet.
+
+With ``disturb`` (a DisturbParams; needs ``plant`` and ``episode``) the tick starts with the disturbance stage: per
+robot it draws this tick's push, the weight of the episode's payload and the sensor noise with the episode's IMU
+biases, all functions of the seed, the robot and the episode slot's episode index and tick.  The plant applies
+``wrench``; the estimator and the policy stage read ``sensors_noisy``, while the plant keeps writing, and the
+episode stage keeps reading, the clean ``sensors``.
 """
 from . import _lib
 from .balance import assemble_balance_device, default_balance_gains
 from .command import command_device, command_state_size
+from .disturb import DO_SIZE, PW_SIZE, DisturbParams, disturb_buffers, disturb_device, plant_step_wrench_device
 from .episode import (EL_SIZE, ET_SIZE, POOL_INIT, POOL_SIZE, SEG_SIZE, EpisodeParams, episode_buffers, episode_device,
                       episode_state_size)
 from .estimator import estimator_state_size, state_estimate_device
@@ -63,7 +70,8 @@ from .torques import joint_torques_device
 class ControlTick:
     def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None, command=None,
                  control_type=None, balance=None, gains=None, policy=None, plant=None, plant_init=None,
-                 episode=None, episode_pool=None, episode_scripts=None, episode_log_len=4):
+                 episode=None, episode_pool=None, episode_scripts=None, episode_log_len=4, disturb=None,
+                 disturb_dirs=None):
         """control_type: None = the MPC-only tick; 0 / 1 = every robot takes the balance / the MPC branch;
         2 (with ``policy``) = every robot takes the policy branch;
         "per_robot" = the tick owns ``self.control_type``, an int32 [B] device tensor the caller writes
@@ -83,7 +91,12 @@ class ControlTick:
         pack_episode_scripts, or None) and ``plant_init`` (pool row 0 until the first draw, unless ``plant_init``
         is given).  Every robot starts fresh, so neither ``plant_init`` nor ``prime_plant()`` is needed: tick 1
         draws, tick 2 primes, tick 3 is episode tick 0.  The counts, ``dt`` and ``log_len`` of the params are
-        set by the tick."""
+        set by the tick.
+        ``disturb`` (a DisturbParams; needs ``plant`` and ``episode``; ``disturb_dirs``, rows [D, 4] of
+        pack_push_dirs, when it pushes): the tick starts with the disturbance stage and owns ``wrench``,
+        ``disturb_out`` and, when it has ``sensors``, ``sensors_noisy``, which the estimator and the policy stage
+        then read.  ``dir_count`` of the params is set by the tick; the seed is the params' own.  With the
+        default (all-off) params every buffer is bitwise that of the tick without ``disturb``."""
         import torch
         self.torch = torch
         self.B = int(batch)
@@ -188,17 +201,38 @@ class ControlTick:
                 size("plan_state"), ptr("cmd_state"), size("cmd_state"), ptr("policy_state"), size("policy_state"),
                 ptr("warm"), size("warm"))
             self.episode = ep
+        self.disturb = None
+        if disturb is not None:
+            if plant is None or self.episode is None:
+                raise ValueError("ControlTick(disturb=...) needs plant= and episode=")
+            dp = DisturbParams.from_buffer_copy(disturb)
+            self.disturb_dirs = None
+            dp.dir_count = 0
+            if disturb_dirs is not None:
+                dirs = torch.as_tensor(disturb_dirs, dtype=torch.float64).reshape(-1, 4)
+                dp.dir_count = dirs.shape[0]
+                self.disturb_dirs = dirs.to(dev).contiguous()
+            self.wrench = torch.zeros((self.B, PW_SIZE), **f64)
+            self.disturb_out = torch.zeros((self.B, DO_SIZE), **f64)
+            if hasattr(self, "sensors"):
+                self.sensors_noisy = torch.zeros((self.B, _lib.SN_SIZE), **f64)
+            ptr = lambda name: getattr(self, name).data_ptr() if getattr(self, name, None) is not None else 0
+            self.disturb_buffers = disturb_buffers(ptr("episode_state"), ptr("wrench"), ptr("sensors"),
+                                                   ptr("sensors_noisy"), ptr("disturb_dirs"), ptr("disturb_out"))
+            self.disturb = dp
         self.graph = None
 
     def step(self, stream=None, episode=True):
         """Enqueue one tick on `stream` (default: torch's current stream).  ``episode=False`` leaves the episode
         stage out, for a caller that reads the tick's rows before enqueueing it with ``episode_stage()``."""
         s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        if self.disturb is not None:
+            self.disturb_stage(s)
         if self.command is not None:
             command_device(self.command, self.dt, self.cmd.data_ptr(), self.states.data_ptr(),
                            self.plan_in.data_ptr(), self.B, self.cmd_state.data_ptr(), s)
         if self.estimator is not None:
-            state_estimate_device(self.estimator, self.dt, self.sensors.data_ptr(), self.plan_in.data_ptr(),
+            state_estimate_device(self.estimator, self.dt, self._sensed().data_ptr(), self.plan_in.data_ptr(),
                                   self.states.data_ptr(), self.B, self.est_state.data_ptr(),
                                   self.tq_records.data_ptr(), self.est_out.data_ptr(), s)
         if self.typed:
@@ -216,6 +250,15 @@ class ControlTick:
         if self.episode is not None and episode:
             self.episode_stage(s)
 
+    def disturb_stage(self, stream=None):
+        """Enqueue the disturbance stage alone: first in the tick (``disturb_buffers``)."""
+        s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+        disturb_device(self.disturb, self.disturb_buffers, self.B, s)
+
+    def _sensed(self):
+        """The sensor row the controller's stages read: the noisy one with the disturbance stage."""
+        return self.sensors_noisy if self.disturb is not None else self.sensors
+
     def episode_stage(self, stream=None):
         """Enqueue the episode stage alone: last in the tick, on whichever of the sensors, cmd and slot buffers
         the tick has (``episode_buffers``)."""
@@ -227,11 +270,14 @@ class ControlTick:
         With the estimator it writes what sensors would deliver; without it, also the truth image of what the
         estimator would write."""
         truth = self.estimator is None
-        plant_step_device(self.plant, self.dt, self.torques.data_ptr(), self.B, self.plant_state.data_ptr(),
-                          self.plant_init.data_ptr() if self.plant_init is not None else 0,
-                          self.sensors.data_ptr() if hasattr(self, "sensors") else 0, self.plan_in.data_ptr(),
-                          self.states.data_ptr() if truth else 0, self.tq_records.data_ptr() if truth else 0,
-                          self.plant_out.data_ptr(), s)
+        rows = (self.B, self.plant_state.data_ptr(), self.plant_init.data_ptr() if self.plant_init is not None else 0,
+                self.sensors.data_ptr() if hasattr(self, "sensors") else 0, self.plan_in.data_ptr(),
+                self.states.data_ptr() if truth else 0, self.tq_records.data_ptr() if truth else 0,
+                self.plant_out.data_ptr(), s)
+        if self.disturb is not None:
+            plant_step_wrench_device(self.plant, self.dt, self.torques.data_ptr(), self.wrench.data_ptr(), *rows)
+        else:
+            plant_step_device(self.plant, self.dt, self.torques.data_ptr(), *rows)
 
     def prime_plant(self, stream=None):
         """Enqueue the plant stage alone.  On fresh slots (after construction or a reset) it initialises them from
@@ -260,7 +306,7 @@ class ControlTick:
         joint_torques_device(self.tq_records.data_ptr(), self.results.data_ptr(), self.B, self.counter.data_ptr(),
                              self.torques.data_ptr(), s)
         if self.policy is not None:
-            policy_device(self.policy, self.sensors.data_ptr(), self.states.data_ptr(), self.plan_in.data_ptr(),
+            policy_device(self.policy, self._sensed().data_ptr(), self.states.data_ptr(), self.plan_in.data_ptr(),
                           self.cmd.data_ptr(), self.B, self.policy_state.data_ptr(), self.torques.data_ptr(),
                           self.policy_out.data_ptr(), ty, 2, s)
         if self.plant is not None:

@@ -897,6 +897,126 @@ int32_t mpcqp_episode_buffers_size(void); /* sizeof(mpcqp_episode_buffers), for 
 int32_t mpcqp_episode_device(const mpcqp_episode_params* ep, const mpcqp_episode_buffers* buf, int32_t batch,
                              double* d_episode_state, void* stream);
 
+/* ---- disturbance stage: the first stage of a tick that has the plant and the episode stage.  It draws, on the
+ * device, what the world does to each robot this tick: a push, the weight of a payload, and sensor noise with
+ * IMU biases.  The plant takes the first two through a wrench row; the estimator and the policy stage read the
+ * third as a second, noisy sensor row.
+ *
+ * Wrench row d_wrench [batch][MPCQP_PW_SIZE]: two applied forces, each a world-frame force and a body-frame
+ * application point relative to the trunk's centre of mass.                                                 */
+#define MPCQP_PW_FORCE0 0        /* [3] force 0, world (the disturbance stage: the push)                   */
+#define MPCQP_PW_POINT0 3        /* [3] its application point, body frame                                  */
+#define MPCQP_PW_FORCE1 6        /* [3] force 1, world (the disturbance stage: the payload's weight)       */
+#define MPCQP_PW_POINT1 9        /* [3] its application point, body frame                                  */
+#define MPCQP_PW_SIZE 12
+
+/* mpcqp_plant_step_device with external forces.  d_wrench == NULL is mpcqp_plant_step_device, bit for bit.  With
+ * a row F0, p0, F1, p1, step 3 of every substep becomes, with that substep's R and contraction off,
+ *     Fe   = F0 + F1                              (per component)
+ *     F    = ((f_0 + f_1) + (f_2 + f_3)) + Fe     (the legs' sum first, as without a wrench)
+ *     Fb_i = R' F_i,  c_i = p_i x Fb_i            (R' v and a x b as everywhere in the plant)
+ *     Ce   = c_0 + c_1                            (per component)
+ *     Mb   = R' M + Ce                            (M the legs' moment sum, as without a wrench)
+ *     wd   = I^-1 (Mb - w x I w)
+ * and nothing else changes.  A component of Fe or Ce that compares equal to zero is skipped, not added (x + 0.0
+ * would turn a sum that is exactly -0.0, which a robot standing under zero torques produces, into +0.0): so an
+ * all-zero row, too, leaves every bit as mpcqp_plant_step_device computes it.  The row is held over the tick's
+ * substeps, like the torque row.  A non-finite wrench row is treated like a non-finite torque row: 3.0 in
+ * MPCQP_PT_STATUS and nothing else written that tick.  The forces model what pushes or loads the trunk; they
+ * carry no mass, so a payload's weight is modelled and its inertia is not.                                  */
+int32_t mpcqp_plant_step_wrench_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                       const double* d_wrench, int32_t batch, double* d_plant_state,
+                                       const double* d_plant_init, double* d_sensors, double* d_plan_in,
+                                       double* d_states, double* d_tq_records, double* d_plant_out, void* stream);
+
+/* The stage is stateless: every draw is a function of the Philox key `seed`, the robot index, and
+ * MPCQP_ES_EPISODE / MPCQP_ES_TICK of the robot's episode slot, which it only reads.  So a restart needs no
+ * zero-fill, and the host can recompute what any logged episode was subjected to.  Philox4x32-10 with
+ * key = seed[0], seed[1] and counter = (robot, episode, stream, index); the episode stage's own draw is stream
+ * 0, index 0.  With the output words w0..w3, u(w) = (w + 0.5) 2^-32 in (0, 1) and s(w) = (w + 0.5) 2^-31 - 1 in
+ * (-1, 1), both exact, and t = MPCQP_ES_TICK, a robot in phase 1 gets:
+ *   load     (stream 1, index 0; once per episode) the downward force m g, m = load_mass_max u(w0), g = gravity,
+ *            computed as (load_mass_max u(w0)) gravity, at the body point load_point[i] s(w_{i+1}); force slot 1
+ *            of the wrench row is (0, 0, 0 - m g).  The payload's weight only, not its inertia.
+ *   biases   (stream 1, index 1 and 2; once per episode) bias_acc s(w_i) and bias_gyro s(w_i), i = 0..2.
+ *   push     (stream 2, index k) if push_interval > 0 and t >= push_start: r = t - push_start, window
+ *            k = r / push_interval, jitter = (uint64(w0) (push_interval - push_duration + 1)) >> 32; the push is
+ *            active while jitter <= r % push_interval < jitter + push_duration, so a window holds one push and
+ *            pushes never overlap.  Magnitude push_force[0] + (push_force[1] - push_force[0]) u(w1); direction
+ *            row (uint64(w2) dir_count) >> 32 of d_dirs [dir_count][4], unit vectors in the world frame that the
+ *            host builds (no trigonometry runs here); application point (stream 3, index k)
+ *            push_point[i] s(w_i).  Force slot 0 of the wrench row is magnitude * direction at that point while
+ *            the push is active, and zero otherwise.
+ *   noise    (stream 16 + j, index t, j = 0..29 over the sensor doubles MPCQP_SN_JOINT_POS + j: 12 joint
+ *            angles, 12 joint rates, imu_acc, imu_ang_vel) z = ((u(w0) + u(w1)) + (u(w2) + u(w3))) - 2, an
+ *            Irwin-Hall variate of variance 1/3, so no log, sin or cos is needed; d = (sigma 1.7320508075688772) z
+ *            for a joint value and bias + (sigma 1.7320508075688772) z for an IMU value, sigma the value's group
+ *            (MPCQP_DS_*); the noisy value is clean + d, and the clean value's own bits when d == 0.  Written out
+ *            of place: d_sensors is read, d_sensors_noisy written, the quaternion and the pad copied.  The clean
+ *            row stays what the plant wrote (the episode stage's energy keeps reading the truth, and a robot
+ *            whose plant tick wrote nothing is not noised twice).
+ * A robot whose phase is not 1 (fresh or priming) gets a zero wrench row, a zero output row and a plain copy of
+ * its sensor row.  Integer and binary64 multiplies and adds only, not contracted, no libm call, in the
+ * statement order of tests/disturb_reference.py: the two agree bitwise.
+ * Left out: noise on the quaternion and on MPCQP_PL_FOOT_FORCE (the plant writes the foot force in place and two
+ * stages read it), the payload's inertia, per-robot plant mass and friction, terrain, foot slip.             */
+#define MPCQP_DS_JOINT_POS 0     /* indices of mpcqp_disturb_params.sigma                                  */
+#define MPCQP_DS_JOINT_VEL 1
+#define MPCQP_DS_IMU_ACC 2
+#define MPCQP_DS_IMU_ANG_VEL 3
+typedef struct mpcqp_disturb_params {
+  double load_mass_max;    /* kg; the payload's mass is uniform in (0, load_mass_max).  0                    */
+  double gravity;          /* 9.81                                                                         */
+  double load_point[3];    /* half-extents of the box, body frame, the payload's point is drawn from.  0    */
+  double bias_acc;         /* IMU biases, uniform in (-bias, bias) per axis.  0                             */
+  double bias_gyro;
+  double push_force[2];    /* N, lowest and highest push magnitude.  0, 0                                   */
+  double push_point[3];    /* half-extents of the box the push's application point is drawn from.  0        */
+  double sigma[4];         /* standard deviations of the noise, per group MPCQP_DS_*.  0                    */
+  uint32_t seed[2];        /* the Philox key (the episode stage's, for one stream of draws per fleet)       */
+  int32_t push_start;      /* first episode tick of window 0.  0                                           */
+  int32_t push_interval;   /* ticks per window; 0: no pushes.  0                                           */
+  int32_t push_duration;   /* ticks per push, 1 .. push_interval.  1                                       */
+  int32_t dir_count;       /* rows of d_dirs.  0                                                           */
+} mpcqp_disturb_params;
+
+void mpcqp_disturb_default_params(mpcqp_disturb_params* p); /* everything off */
+int32_t mpcqp_disturb_params_size(void);  /* sizeof(mpcqp_disturb_params), for bindings */
+
+/* Optional output row d_disturb_out [batch][MPCQP_DO_SIZE]: what the robot was subjected to this tick. */
+#define MPCQP_DO_PUSH_ACTIVE 0   /* 1.0 while a push acts                                                  */
+#define MPCQP_DO_PUSH_WINDOW 1   /* k; this and the next three describe the window's push, active or not,  */
+#define MPCQP_DO_PUSH_FORCE 2    /* its magnitude                 and are 0 before push_start / without pushes */
+#define MPCQP_DO_PUSH_DIR 3      /* its row of d_dirs                                                      */
+#define MPCQP_DO_PUSH_POINT 4    /* [3] its application point                                              */
+#define MPCQP_DO_LOAD_POINT 7    /* [3] the payload's point                                                */
+#define MPCQP_DO_LOAD_FORCE 10   /* the payload's weight m g (the wrench row holds 0 - m g in z)           */
+#define MPCQP_DO_BIAS_ACC 11     /* [3]                                                                    */
+#define MPCQP_DO_BIAS_GYRO 14    /* [3]                                                                    */
+#define MPCQP_DO_SIZE 20         /* 17 used, padded to a multiple of 4 doubles                             */
+
+/* The stage's buffers (DEVICE pointers).  d_sensors and d_sensors_noisy may both be NULL (a truth-fed tick:
+ * pushes and load only), d_dirs may be NULL when push_interval == 0, d_disturb_out may be NULL.             */
+typedef struct mpcqp_disturb_buffers {
+  const double* d_episode_state; /* [batch][MPCQP_ES_SIZE]  MPCQP_ES_PHASE, _TICK, _EPISODE read; a stand-alone
+                                    caller hands a hand-made row                                           */
+  double* d_wrench;              /* [batch][MPCQP_PW_SIZE]  written                                        */
+  const double* d_sensors;       /* [batch][MPCQP_SN_SIZE]  read                                           */
+  double* d_sensors_noisy;       /* [batch][MPCQP_SN_SIZE]  written; must not be d_sensors                 */
+  const double* d_dirs;          /* [dir_count][4]          x, y, z, 0                                     */
+  double* d_disturb_out;         /* [batch][MPCQP_DO_SIZE]  written                                        */
+} mpcqp_disturb_buffers;
+int32_t mpcqp_disturb_buffers_size(void); /* sizeof(mpcqp_disturb_buffers), for bindings */
+
+/* One disturbance tick for `batch` robots (DEVICE pointers, async on `stream`, no allocation and no
+ * synchronization: hipGraph-capture safe; one kernel).  Chain it first in the tick, and give the plant stage
+ * d_wrench through mpcqp_plant_step_wrench_device.  The structs are read when the call is made.
+ * MPCQP_ERR_INVALID_ARG, and nothing launched: a NULL episode slot or wrench row; one of d_sensors /
+ * d_sensors_noisy without the other, or the two equal; push_interval < 0; with push_interval > 0,
+ * push_duration outside 1 .. push_interval, push_start < 0, d_dirs NULL or dir_count < 1.                    */
+int32_t mpcqp_disturb_device(const mpcqp_disturb_params* dp, const mpcqp_disturb_buffers* buf, int32_t batch,
+                             void* stream);
+
 const char* mpcqp_status_str(int32_t status);
 const char* mpcqp_error_str(int32_t err);
 /* Last HIP error string recorded by the handle (for MPCQP_ERR_HIP). */

@@ -18,6 +18,15 @@ rows, a time-out, an envelope; not in the default list), four more:
   full_walk  the full setup under a script that toggles walk mode and commands 0.3 m/s forward at episode tick 100
   servo_ep   the servo setup: the fleet that sinks and falls, restarted and counted
 
+and, with the disturbance stage as the tick's first stage (ControlTick(disturb=)), two more on the full_ep setup:
+
+  full_push  one push per episode: PUSH_TICKS ticks long, starting at a drawn tick from episode tick PUSH_START on,
+             of a magnitude uniform in PUSH_FORCE, in one of 16 horizontal directions, at the centre of mass.  Its
+             line carries the push-recovery curve: per push-magnitude bin, the share of logged episodes ended by
+             the envelope or a plant status, from the log rows and mpcqp.disturbance_of
+  full_noise sensor noise NOISE_SIGMA (joint angles, joint rates, accelerometer, gyro) and IMU biases up to
+             NOISE_BIAS per axis, redrawn every episode
+
 These report episodes completed, the end-reason histogram, ticks/s and medians of the logged episodes' metrics
 from the device's totals and log, read once after the last replay; they never rerun with a read per tick.
 
@@ -126,7 +135,9 @@ def episode_pool(P, q_leg, tilt, seed, height=None):
     return mpcqp.pack_episode_pool(init, np.stack([zero, zero, e[:, 2]], 1), np.stack([zero, zero, z], 1))
 
 
-EPISODE_FORMS = ("mpc_ep", "full_ep", "full_walk", "servo_ep")
+EPISODE_FORMS = ("mpc_ep", "full_ep", "full_walk", "servo_ep", "full_push", "full_noise")
+PUSH_START, PUSH_TICKS, PUSH_FORCE, PUSH_DIRS, PUSH_BIN = 100, 40, (0.0, 300.0), 16, 25.0
+NOISE_SIGMA, NOISE_BIAS = (0.005, 0.1, 0.2, 0.02), (0.1, 0.01)
 POOL, MAX_TICKS, WALK_AT, WALK_VX = 64, 500, 100, 0.3
 
 
@@ -161,6 +172,15 @@ def make_episode(form, B, seed):
         over = {}
         scripts = mpcqp.pack_episode_scripts([[(0, (0, 0, 0), (0, 0, 0), False),
                                                (WALK_AT, (WALK_VX, 0, 0), (0, 0, 0), True)]])
+    if form == "full_push":
+        # one window per episode: it starts at PUSH_START and is as long as what is left of the episode
+        kw.update(disturb=mpcqp.default_disturb_params(seed=seed, push_force=PUSH_FORCE, push_start=PUSH_START,
+                                                       push_interval=max(MAX_TICKS - PUSH_START, PUSH_TICKS),
+                                                       push_duration=PUSH_TICKS),
+                  disturb_dirs=mpcqp.pack_push_dirs(PUSH_DIRS))
+    elif form == "full_noise":
+        kw.update(disturb=mpcqp.default_disturb_params(seed=seed, sigma=NOISE_SIGMA, bias_acc=NOISE_BIAS[0],
+                                                       bias_gyro=NOISE_BIAS[1]))
     ep = mpcqp.default_episode_params(max_ticks=MAX_TICKS, tilt_max=0.3, seed=seed, **over)
     k = ControlTick(B, dt=DT, plant=pp, episode=ep, episode_pool=pool, episode_scripts=scripts, episode_log_len=8,
                     **kw)
@@ -188,6 +208,7 @@ def run_episode(form, B, T, seed):
         tot = np.frombuffer(k.episode_totals.cpu().numpy().tobytes(), dtype=mpcqp.EPISODE_TOTALS_DTYPE)
         log = np.frombuffer(k.episode_log.cpu().numpy().tobytes(), dtype=mpcqp.EPISODE_LOG_DTYPE)
         es = np.frombuffer(k.episode_state.cpu().numpy().tobytes(), dtype=mpcqp.EPISODE_STATE_DTYPE)
+        robot = np.repeat(np.arange(B), k.episode_log.shape[1])[log["length"] > 0]
         log = log[log["length"] > 0]
         r = {"form": form, "batch": B, "ticks": T, "dt": DT, "ticks_per_s": T / (ms * 1e-3),
              "robot_ticks_per_s": B * T / (ms * 1e-3), "ms_per_tick": ms / T, "max_ticks": MAX_TICKS, "pool": POOL,
@@ -204,6 +225,10 @@ def run_episode(form, B, T, seed):
                           "err_vx_rms_median": float(np.sqrt(np.nanmedian(log["err_v"][:, 0] / log["length"]))),
                           "not_solved_share": float(log["not_solved"].sum() / log["length"].sum()),
                           "low_contact_share": float(log["low_contact"].sum() / log["length"].sum())})
+                if form == "full_push":
+                    r.update(push_curve(k, robot, log))
+                if form == "full_noise":
+                    r.update({"noise_sigma": list(NOISE_SIGMA), "noise_bias": list(NOISE_BIAS)})
                 if form == "full_walk":
                     d = log["end"][:, :2] - log["start"][:, :2]
                     yaw = log["start"][:, 2]
@@ -221,6 +246,31 @@ def run_episode(form, B, T, seed):
         if extra is not None:
             extra.close()
     return r
+
+
+def push_curve(k, robot, log):
+    """The push-recovery curve of the logged episodes: each episode's push recomputed on the host from the seed, the
+    robot and the episode index; per magnitude bin the episodes and how many ended by the envelope or a plant
+    status.  An episode that ended before its push began is counted apart."""
+    from mpcqp import episode as me
+    dirs = k.disturb_dirs.cpu().numpy()
+    force, failed, before = [], [], 0
+    for b, row in zip(robot, log):
+        pushes = mpcqp.disturbance_of(k.disturb, dirs, int(b), int(row["episode"]), int(row["length"]))["pushes"]
+        if not pushes:
+            before += 1
+            continue
+        force.append(pushes[0]["force"])
+        failed.append(int(row["reason"]) in (me.END_OUT_OF_REACH, me.END_FALLEN, me.END_BAD_TORQUE, me.END_ENVELOPE))
+    force, failed = np.array(force), np.array(failed, dtype=bool)
+    edges = np.arange(PUSH_FORCE[0], PUSH_FORCE[1] + PUSH_BIN, PUSH_BIN)
+    curve = []
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        m = (force >= lo) & (force < hi)
+        curve.append({"force_lo": float(lo), "force_hi": float(hi), "episodes": int(m.sum()),
+                      "failed": int(failed[m].sum()), "failed_share": float(failed[m].mean()) if m.any() else None})
+    return {"push_start": PUSH_START, "push_ticks": PUSH_TICKS, "push_force": list(PUSH_FORCE), "push_dirs": PUSH_DIRS,
+            "episodes_ended_before_their_push": before, "push_recovery_curve": curve}
 
 
 def look(k, stand_z):
