@@ -433,18 +433,38 @@ def load(debug=False):
     return L
 
 
+def override(struct, over, special=None):
+    """Apply keyword overrides to a parameter structure and return it.  A c_double array field takes anything that
+    flattens to exactly its length; any other field is set; a name that is not a field raises AttributeError
+    (setattr on a ctypes structure would accept and ignore it).  ``special`` maps a name to ``set(struct, value)``
+    for the overrides that are not a plain field assignment."""
+    fields = dict(struct._fields_)
+    for k, v in over.items():
+        if special and k in special:
+            special[k](struct, v)
+        elif k not in fields:
+            raise AttributeError(f"{type(struct).__name__} has no field {k!r}")
+        elif issubclass(fields[k], ctypes.Array) and fields[k]._type_ is ctypes.c_double:
+            arr = getattr(struct, k)
+            flat = np.asarray(v, dtype=np.float64).reshape(-1)
+            if flat.size != len(arr):
+                raise ValueError(f"{k}: expected {len(arr)} values, got {flat.size}")
+            arr[:] = flat.tolist()
+        else:
+            setattr(struct, k, v)
+    return struct
+
+
+def set_seed(struct, v):
+    """The ``seed`` override of the episode and disturbance parameters: one 64-bit integer into uint32[2]."""
+    struct.seed[0], struct.seed[1] = int(v) & 0xFFFFFFFF, (int(v) >> 32) & 0xFFFFFFFF
+
+
 def default_params(horizon=10, **over):
     """mpcqp_default_params + keyword overrides (q_weights/r_weights accept sequences)."""
     p = Params()
     load().mpcqp_default_params(ctypes.byref(p), horizon)
-    for k, v in over.items():
-        if k in ("q_weights", "r_weights"):
-            arr = getattr(p, k)
-            for i, x in enumerate(v):
-                arr[i] = float(x)
-        else:
-            setattr(p, k, v)
-    return p
+    return override(p, over)
 
 
 def assemble_records_device(horizon, d_states, batch, d_records, stream=0):
@@ -464,13 +484,7 @@ def default_balance_params(**over):
     """mpcqp_balance_default_params (A1RobotControl.cpp:11-15) + keyword overrides."""
     bp = BalanceParams()
     load().mpcqp_balance_default_params(ctypes.byref(bp))
-    for k, v in over.items():
-        if k == "q_diag":
-            for i, x in enumerate(v):
-                bp.q_diag[i] = float(x)
-        else:
-            setattr(bp, k, v)
-    return bp
+    return override(bp, over)
 
 
 def check(rc, handle=None, what="mpcqp", lib=None):

@@ -10,7 +10,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import BalanceGains, check, default_balance_params, load  # noqa: F401  (default_balance_params: re-export)
+from ._lib import BalanceGains, check, default_balance_params, load, override  # noqa: F401  (default_balance_params: re-export)
 from .records import GO1_MASS, RobotStates
 
 BAL_POS, BAL_POS_D, BAL_ROT, BAL_ROT_Z = 0, 3, 6, 15
@@ -65,14 +65,7 @@ def default_balance_gains(**over):
     (each a sequence of 3)."""
     g = BalanceGains()
     load().mpcqp_balance_default_gains(ctypes.byref(g))
-    for k, v in over.items():
-        arr = getattr(g, k)
-        flat = np.asarray(v, dtype=np.float64).reshape(-1)
-        if flat.size != 3:
-            raise ValueError(f"{k}: expected 3 values, got {flat.size}")
-        for i, x in enumerate(flat):
-            arr[i] = float(x)
-    return g
+    return override(g, over)
 
 
 def assemble_balance_device(gains, d_states, d_plan_in, d_cmd_state, batch, d_bal_records, stream=0):

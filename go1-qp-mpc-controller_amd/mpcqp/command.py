@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import CM_MODE_REQUEST, CM_RATE, CM_SIZE, CM_VEL, CommandParams, check, load
+from ._lib import CM_MODE_REQUEST, CM_RATE, CM_SIZE, CM_VEL, CommandParams, check, load, override
 
 # the slot (include/mpcqp.h MPCQP_CS_*); flags and states as 0.0 / 1.0
 CMD_STATE_DTYPE = np.dtype([
@@ -27,16 +27,7 @@ def default_command_params(**over):
     Go1CtrlStates.hpp:279-281, :304-305) + keyword overrides (kp_linear: a sequence of 3)."""
     p = CommandParams()
     load().mpcqp_command_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k == "kp_linear":
-            flat = np.asarray(v, dtype=np.float64).reshape(-1)
-            if flat.size != 3:
-                raise ValueError(f"kp_linear: expected 3 values, got {flat.size}")
-            for i, x in enumerate(flat):
-                p.kp_linear[i] = float(x)
-        else:
-            setattr(p, k, v)
-    return p
+    return override(p, over)
 
 
 def command_state_size():

@@ -15,7 +15,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import DisturbBuffers, DisturbParams, check, load
+from ._lib import DisturbBuffers, DisturbParams, check, load, override, set_seed
 
 # include/mpcqp.h MPCQP_PW_*, MPCQP_DO_*, MPCQP_DS_*
 PW_FORCE0, PW_POINT0, PW_FORCE1, PW_POINT1, PW_SIZE = 0, 3, 6, 9, 12
@@ -29,26 +29,11 @@ DISTURB_OUT_DTYPE = np.dtype([
 ])
 assert DISTURB_OUT_DTYPE.itemsize == 8 * DO_SIZE
 
-_ARRAYS = ("load_point", "push_force", "push_point", "sigma")
-
-
 def default_disturb_params(**over):
     """mpcqp_disturb_default_params (everything off) + keyword overrides; ``seed`` is one 64-bit integer."""
     p = DisturbParams()
     load().mpcqp_disturb_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k == "seed":
-            p.seed[0], p.seed[1] = int(v) & 0xFFFFFFFF, (int(v) >> 32) & 0xFFFFFFFF
-        elif k in _ARRAYS:
-            arr = getattr(p, k)
-            flat = np.asarray(v, dtype=np.float64).reshape(-1)
-            if flat.size != len(arr):
-                raise ValueError(f"{k}: expected {len(arr)} values, got {flat.size}")
-            for i, x in enumerate(flat):
-                arr[i] = float(x)
-        else:
-            setattr(p, k, v)
-    return p
+    return override(p, over, {"seed": set_seed})
 
 
 def pack_push_dirs(count):

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import EpisodeBuffers, EpisodeParams, check, load
+from ._lib import EpisodeBuffers, EpisodeParams, check, load, override, set_seed
 
 # include/mpcqp.h MPCQP_EP_*, MPCQP_ES_*, MPCQP_EM_*, MPCQP_EL_*, MPCQP_ET_*
 END_FRESH, END_OUT_OF_REACH, END_FALLEN, END_BAD_TORQUE, END_ENVELOPE, END_TIMEOUT, END_COUNT = 0, 1, 2, 3, 4, 5, 6
@@ -37,12 +37,7 @@ def default_episode_params(**over):
     """mpcqp_episode_default_params + keyword overrides; ``seed`` is one 64-bit integer."""
     p = EpisodeParams()
     load().mpcqp_episode_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k == "seed":
-            p.seed[0], p.seed[1] = int(v) & 0xFFFFFFFF, (int(v) >> 32) & 0xFFFFFFFF
-        else:
-            setattr(p, k, v)
-    return p
+    return override(p, over, {"seed": set_seed})
 
 
 def episode_state_size():

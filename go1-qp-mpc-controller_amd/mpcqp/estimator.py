@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (SN_IMU_ACC, SN_IMU_ANG_VEL, SN_JOINT_POS, SN_JOINT_VEL, SN_QUAT, SN_SIZE, EstimatorParams, check,
-                   load)
+                   load, override)
 
 # the output row (include/mpcqp.h MPCQP_EO_*)
 EST_OUT_DTYPE = np.dtype([
@@ -26,25 +26,12 @@ assert EST_OUT_DTYPE.itemsize == 8 * _lib.EO_SIZE
 # slot layout (csrc/mpcqp_estimate.hip ES_*)
 _ES_INIT, _ES_X, _ES_P, _NS = 0, 4, 24, 18
 
-_ARRAYS = ("rho_fix", "rho_opt")
-
-
 def default_estimator_params(**over):
     """mpcqp_est_default_params (GazeboA1ROS.cpp:72-98, A1BasicEKF.h:16-21) + keyword overrides; rho_fix
     accepts anything that flattens to [4][5], rho_opt to [4][3]."""
     p = EstimatorParams()
     load().mpcqp_est_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k in _ARRAYS:
-            arr = getattr(p, k)
-            flat = np.asarray(v, dtype=np.float64).reshape(-1)
-            if flat.size != len(arr):
-                raise ValueError(f"{k}: expected {len(arr)} values, got {flat.size}")
-            for i, x in enumerate(flat):
-                arr[i] = float(x)
-        else:
-            setattr(p, k, v)
-    return p
+    return override(p, over)
 
 
 def estimator_state_size():

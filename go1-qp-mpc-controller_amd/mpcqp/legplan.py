@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import PL_FOOT_FORCE, PL_MOVEMENT_MODE, PL_ROT_Z, PL_SIZE, PlanParams, check, load
+from ._lib import PL_FOOT_FORCE, PL_MOVEMENT_MODE, PL_ROT_Z, PL_SIZE, PlanParams, check, load, override
 
 # the output row (include/mpcqp.h MPCQP_PO_*), [leg][xyz] where 12 wide, flags as 0.0 / 1.0
 PLAN_OUT_DTYPE = np.dtype([
@@ -25,25 +25,12 @@ PLAN_OUT_DTYPE = np.dtype([
 ])
 assert PLAN_OUT_DTYPE.itemsize == 8 * _lib.PO_SIZE
 
-_ARRAYS = ("default_foot_pos", "kp_foot", "kd_foot", "gait_counter_speed", "gait_counter_init")
-
-
 def default_plan_params(**over):
     """mpcqp_plan_default_params (A1CtrlStates::reset(), A1Params.h:38-45) + keyword overrides; the
     [4][3] fields accept anything that flattens to 12 values leg-major."""
     p = PlanParams()
     load().mpcqp_plan_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k in _ARRAYS:
-            arr = getattr(p, k)
-            flat = np.asarray(v, dtype=np.float64).reshape(-1)
-            if flat.size != len(arr):
-                raise ValueError(f"{k}: expected {len(arr)} values, got {flat.size}")
-            for i, x in enumerate(flat):
-                arr[i] = float(x)
-        else:
-            setattr(p, k, v)
-    return p
+    return override(p, over)
 
 
 def plan_state_size():

@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import PI_JOINT_POS, PI_POS, PI_QUAT, PI_SIZE, PlantParams, check, load
+from ._lib import PI_JOINT_POS, PI_POS, PI_QUAT, PI_SIZE, PlantParams, check, load, override
 
 # the slot (include/mpcqp.h MPCQP_PN_*) and the output row (MPCQP_PT_*)
 PLANT_STATE_DTYPE = np.dtype([
@@ -32,25 +32,12 @@ assert PLANT_OUT_DTYPE.itemsize == 8 * _lib.PT_SIZE
 
 PLANT_OK, PLANT_OUT_OF_REACH, PLANT_FALLEN, PLANT_BAD_TORQUE = 0, 1, 2, 3
 
-_ARRAYS = ("rho_fix", "rho_opt", "inertia", "joint_inertia", "joint_damping", "default_joint_pos")
-
-
 def default_plant_params(**over):
     """mpcqp_plant_default_params + keyword overrides; the array fields accept anything that flattens to
     their size (rho_fix [4][5], rho_opt [4][3], inertia [3][3], ...)."""
     p = PlantParams()
     load().mpcqp_plant_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k in _ARRAYS:
-            arr = getattr(p, k)
-            flat = np.asarray(v, dtype=np.float64).reshape(-1)
-            if flat.size != len(arr):
-                raise ValueError(f"{k}: expected {len(arr)} values, got {flat.size}")
-            for i, x in enumerate(flat):
-                arr[i] = float(x)
-        else:
-            setattr(p, k, v)
-    return p
+    return override(p, over)
 
 
 def plant_state_size():

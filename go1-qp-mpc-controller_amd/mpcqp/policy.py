@@ -13,7 +13,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import PolicyParams, check, load
+from ._lib import PolicyParams, check, load, override
 
 OBS_DIM, ACTION_DIM = 48, 12
 
@@ -30,8 +30,13 @@ POLICY_OUT_DTYPE = np.dtype([
 ])
 assert POLICY_OUT_DTYPE.itemsize == 8 * _lib.PY_SIZE
 
-_ARRAYS = {"obs_scale": 36, "default_joint_pos": 12, "pose_lower": 12, "pose_upper": 12, "kp_walk": 12, "kd_walk": 12,
-           "kp_servo": 12, "kd_servo": 12, "stand_pos": 12}
+def _set_hidden(p, v):
+    widths = [int(x) for x in v]
+    if not 1 <= len(widths) <= 3:
+        raise ValueError(f"hidden: expected 1 to 3 widths, got {len(widths)}")
+    p.n_hidden = len(widths)
+    for i in range(3):
+        p.hidden[i] = widths[i] if i < len(widths) else 0
 
 
 def default_policy_params(**over):
@@ -40,26 +45,7 @@ def default_policy_params(**over):
     ``hidden`` is a sequence of 1 to 3 widths and sets n_hidden; the array fields accept sequences."""
     p = PolicyParams()
     load().mpcqp_policy_default_params(ctypes.byref(p))
-    for k, v in over.items():
-        if k == "hidden":
-            widths = [int(x) for x in v]
-            if not 1 <= len(widths) <= 3:
-                raise ValueError(f"hidden: expected 1 to 3 widths, got {len(widths)}")
-            p.n_hidden = len(widths)
-            for i in range(3):
-                p.hidden[i] = widths[i] if i < len(widths) else 0
-        elif k in _ARRAYS:
-            flat = np.asarray(v, dtype=np.float64).reshape(-1)
-            if flat.size != _ARRAYS[k]:
-                raise ValueError(f"{k}: expected {_ARRAYS[k]} values, got {flat.size}")
-            arr = getattr(p, k)
-            for i, x in enumerate(flat):
-                arr[i] = float(x)
-        else:
-            if not hasattr(p, k):
-                raise AttributeError(k)
-            setattr(p, k, v)
-    return p
+    return override(p, over, {"hidden": _set_hidden})
 
 
 def policy_state_size():

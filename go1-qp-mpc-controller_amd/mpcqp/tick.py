@@ -8,50 +8,52 @@ persistent warm-started solver of A1RobotControl.h:67) followed by compute_joint
 as a HIP graph (torch.cuda.CUDAGraph is hipGraph on ROCm), so a simulator steps with one replay.
 torch is used only to own device buffers and the capture stream.
 
-With ``plan`` (a PlanParams) the tick starts one stage earlier, with the leg plan (update_plan,
-generate_swing_legs_ctrl and the terrain adaptation of compute_grf, A1RobotControl.cpp:148-287,
-:335-376): it fills the contacts, the swing-leg force and root_euler_d[1] of ``states`` /
-``tq_records`` on the device from ``plan_in``.
+The constructor's options add stages around those three.  A tick is the ordered list
 
-With ``estimator`` (an EstimatorParams) it starts another stage earlier, with the state front end (pose
-and IMU callbacks, GazeboA1ROS.cpp:242-307, and A1BasicEKF::update_estimation, A1BasicEKF.cpp:55-164):
-root_euler, root_pos, root_ang_vel, root_lin_vel, root_rot_mat and foot_pos_abs of ``states``,
-root_rot_mat_z of ``plan_in`` and j_foot of ``tq_records`` are computed on the device from ``sensors``
-(quaternion, joint angles and rates, IMU sample) and the foot forces of ``plan_in``, so the caller writes
-only sensor-level state.  The estimator runs before the plan: the plan and the solve see this tick's estimate.
+    disturb, command, estimate, plan, assemble, assemble_balance, balance, solve, torques, policy, plant, episode
 
-With ``command`` (a CommandParams) it starts with the command stage (the joystick command block of
-main_update, GazeboA1ROS.cpp:122-188): the desired velocities, root_euler_d, root_pos_d and movement_mode
-of ``states`` / ``plan_in`` and the position-locked kp_linear of ``cmd_state`` are computed on the device
-from the joystick-level rows ``cmd``.  It runs first, as in the reference: the estimator sees this tick's
-movement_mode, and the position lock reads the previous tick's root_pos.
+of the stages its options switch on (``stages()``); ``step()`` walks it, and nothing else enqueues a tick.
 
-With ``control_type`` each robot takes the stance_leg_control_type branch of its own (A1RobotControl.cpp:377
-QP balance controller, :446 MPC): the tick assembles both kinds of record and runs the balance solve of the
-type-0 robots and the warm MPC solve of the type-1 robots into the one ``results`` buffer, so the stage order
-is command -> estimate -> plan -> assemble (MPC and balance) -> balance solve -> warm MPC solve -> torque map.
+disturb (``disturb``, a DisturbParams; needs ``plant`` and ``episode``): per robot this tick's push, the weight of
+the episode's payload and the sensor noise with the episode's IMU biases, all functions of the seed, the robot and
+the episode slot's episode index and tick.  The plant applies ``wrench``; the estimator and the policy stage read
+``sensors_noisy``, while the plant keeps writing, and the episode stage keeps reading, the clean ``sensors``.
 
-With ``policy`` (a Policy) the tick ends with the policy stage, the reference's third controller (the Go1 RL
-policy and its servo stand, src/go1_rl_ctrl_cpp/src/Go1RLController.cpp:78-166): after the torque map has run
-for every robot, the stage overwrites the ``torques`` row of the robots whose control type is 2 from ``sensors``,
-``states``, ``plan_in`` and ``cmd``.  Robots of type 0 and 1 are untouched by it.
+command (``command``, a CommandParams; the joystick command block of main_update, GazeboA1ROS.cpp:122-188): the
+desired velocities, root_euler_d, root_pos_d and movement_mode of ``states`` / ``plan_in`` and the position-locked
+kp_linear of ``cmd_state`` from the joystick-level rows ``cmd``.  Before the estimator, as in the reference: the
+estimator sees this tick's movement_mode, and the position lock reads the previous tick's root_pos.
 
-With ``plant`` (a PlantParams) the tick ends with the plant stage, which the reference left to Gazebo: a
-rigid-body model (single trunk, massless stance legs, joint-space swing legs, flat ground) moves every robot
-one control period on under the final ``torques`` row and writes the next tick's ``sensors`` and foot forces,
-so T replays are a T-tick closed-loop rollout with no host write in between.  Without ``estimator`` it also
-writes the ground truth of the estimator's fields into ``states`` / ``plan_in`` / ``tq_records``.
+estimate (``estimator``, an EstimatorParams; pose and IMU callbacks, GazeboA1ROS.cpp:242-307, and
+A1BasicEKF::update_estimation, A1BasicEKF.cpp:55-164): root_euler, root_pos, root_ang_vel, root_lin_vel,
+root_rot_mat and foot_pos_abs of ``states``, root_rot_mat_z of ``plan_in`` and j_foot of ``tq_records`` from
+``sensors`` (quaternion, joint angles and rates, IMU sample) and the foot forces of ``plan_in``, so the caller
+writes only sensor-level state.  Before the plan: the plan and the solve see this tick's estimate.
 
-With ``episode`` (an EpisodeParams; needs ``plant``) the tick ends with the episode stage: per robot it accumulates
-the episode's metrics, ends the episode on a plant status, the envelope or the time-out, writes it into
-``episode_log`` / ``episode_totals`` and restarts the robot over two ticks from a row of ``episode_pool`` drawn on
-the device, under one of ``episode_scripts``, so T replays are a Monte-Carlo evaluation of the fleet.
+plan (``plan``, a PlanParams; update_plan, generate_swing_legs_ctrl and the terrain adaptation of compute_grf,
+A1RobotControl.cpp:148-287, :335-376): the contacts, the swing-leg force and root_euler_d[1] of ``states`` /
+``tq_records`` from ``plan_in``.
 
-With ``disturb`` (a DisturbParams; needs ``plant`` and ``episode``) the tick starts with the disturbance stage: per
-robot it draws this tick's push, the weight of the episode's payload and the sensor noise with the episode's IMU
-biases, all functions of the seed, the robot and the episode slot's episode index and tick.  The plant applies
-``wrench``; the estimator and the policy stage read ``sensors_noisy``, while the plant keeps writing, and the
-episode stage keeps reading, the clean ``sensors``.
+assemble_balance, balance (``control_type``): each robot takes the stance_leg_control_type branch of its own
+(A1RobotControl.cpp:377 QP balance controller, :446 MPC).  The tick assembles both kinds of record and runs the
+balance solve of the type-0 robots and the warm MPC solve of the type-1 robots into the one ``results`` buffer.
+Without ``control_type`` the plan and the solve get a null type pointer, which is the untyped entry point.
+
+policy (``policy``, a Policy; the reference's third controller, the Go1 RL policy and its servo stand,
+src/go1_rl_ctrl_cpp/src/Go1RLController.cpp:78-166): after the torque map has run for every robot, the stage
+overwrites the ``torques`` row of the robots whose control type is 2 from ``sensors``, ``states``, ``plan_in`` and
+``cmd``.  Robots of type 0 and 1 are untouched by it.
+
+plant (``plant``, a PlantParams; what the reference left to Gazebo): a rigid-body model (single trunk, massless
+stance legs, joint-space swing legs, flat ground) moves every robot one control period on under the final
+``torques`` row and writes the next tick's ``sensors`` and foot forces, so T replays are a T-tick closed-loop
+rollout with no host write in between.  Without ``estimator`` it also writes the ground truth of the estimator's
+fields into ``states`` / ``plan_in`` / ``tq_records``.
+
+episode (``episode``, an EpisodeParams; needs ``plant``): per robot it accumulates the episode's metrics, ends the
+episode on a plant status, the envelope or the time-out, writes it into ``episode_log`` / ``episode_totals`` and
+restarts the robot over two ticks from a row of ``episode_pool`` drawn on the device, under one of
+``episode_scripts``, so T replays are a Monte-Carlo evaluation of the fleet.
 """
 from . import _lib
 from .balance import assemble_balance_device, default_balance_gains
@@ -60,11 +62,16 @@ from .disturb import DO_SIZE, PW_SIZE, DisturbParams, disturb_buffers, disturb_d
 from .episode import (EL_SIZE, ET_SIZE, POOL_INIT, POOL_SIZE, SEG_SIZE, EpisodeParams, episode_buffers, episode_device,
                       episode_state_size)
 from .estimator import estimator_state_size, state_estimate_device
-from .legplan import leg_plan_device, leg_plan_typed_device, plan_state_size
+from .legplan import leg_plan_typed_device, plan_state_size
 from .plant import plant_state_size, plant_step_device
 from .policy import policy_device, policy_state_size
 from .solver import MpcQpSolver
 from .torques import joint_torques_device
+
+# the stages a caller can leave out (``without=``), and the constructor option each stands for
+_OPTION_OF = dict(disturb="disturb", command="command", estimate="estimator", plan="plan",
+                  assemble_balance="control_type", balance="control_type", policy="policy", plant="plant",
+                  episode="episode")
 
 
 class ControlTick:
@@ -96,234 +103,268 @@ class ControlTick:
         pack_push_dirs, when it pushes): the tick starts with the disturbance stage and owns ``wrench``,
         ``disturb_out`` and, when it has ``sensors``, ``sensors_noisy``, which the estimator and the policy stage
         then read.  ``dir_count`` of the params is set by the tick; the seed is the params' own.  With the
-        default (all-off) params every buffer is bitwise that of the tick without ``disturb``."""
+        default (all-off) params every buffer is bitwise that of the tick without ``disturb``.
+        A buffer the tick does not own is an absent attribute (``_buffers`` has the rule)."""
         import torch
         self.torch = torch
         self.B = int(batch)
+        o = dict(disturb=disturb, command=command, estimator=estimator, plan=plan, control_type=control_type,
+                 policy=policy, plant=plant, episode=episode)
+        tick_dt = self._check(o, dt, episode_pool)
+        if tick_dt is not None:
+            self.dt = tick_dt
         self.solver = MpcQpSolver(params if params is not None else _lib.default_params(10), device=device)
         self.solver.reserve(self.B)
-        N = self.solver.horizon
         dev = f"cuda:{device}"
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.states = torch.zeros((self.B, _lib.ST_SIZE), **f64)        # caller writes robot states here
-        self.tq_records = torch.zeros((self.B, _lib.TQ_SIZE), **f64)    # and Jacobians / swing forces here
-        self.records = torch.zeros((self.B, _lib.rec_size(N)), **f64)
-        self.warm = torch.zeros((self.B, self.solver.warm_state_size), **f64)
-        self.results = torch.zeros((self.B, _lib.RESULT_DOUBLES), **f64)
-        self.counter = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-        self.torques = torch.zeros((self.B, 12), **f64)
-        self.plan = plan
-        if plan is not None:
-            self.dt = float(plan.control_dt if dt is None else dt)  # update_plan's dt argument
-            self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)   # caller writes rot_z / foot_force / mode
-            self.plan_state = torch.zeros((self.B, plan_state_size()), **f64)  # zero = reset() controller
-            self.plan_out = torch.zeros((self.B, _lib.PO_SIZE), **f64)
-        self.estimator = estimator
-        if estimator is not None:
-            if plan is None:
-                if dt is None:
-                    raise ValueError("ControlTick(estimator=...) without plan= needs dt")
-                self.dt = float(dt)  # update_estimation's dt argument
-                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # caller writes foot_force / mode
-            self.sensors = torch.zeros((self.B, _lib.SN_SIZE), **f64)    # caller writes quat / joints / IMU here
-            self.est_state = torch.zeros((self.B, estimator_state_size()), **f64)  # zero = not initialized
-            self.est_out = torch.zeros((self.B, _lib.EO_SIZE), **f64)
-        self.command = command
-        if command is not None:
-            if plan is None and estimator is None:
-                if dt is None:
-                    raise ValueError("ControlTick(command=...) without plan= needs dt")
-                self.dt = float(dt)  # main_update's dt argument
-                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # movement_mode is written here
-            self.cmd = torch.zeros((self.B, _lib.CM_SIZE), **f64)       # caller writes joystick-level commands here
-            self.cmd_state = torch.zeros((self.B, command_state_size()), **f64)  # zero = fresh
-        if control_type not in (None, 0, 1, "per_robot") and not (control_type == 2 and policy is not None):
-            raise ValueError('control_type must be None, 0, 1 or "per_robot" (or 2 with policy=)')
-        if policy is not None and control_type not in ("per_robot", 2):
-            raise ValueError('ControlTick(policy=...) needs control_type="per_robot" or 2')
+        given = lambda rows: torch.as_tensor(rows, dtype=torch.float64)  # a caller's rows, before their reshape
+        self.plan, self.estimator, self.command, self.policy, self.plant = plan, estimator, command, policy, plant
         self.typed = control_type is not None
         if self.typed:
             self.control_type = torch.full((self.B,), 1 if control_type == "per_robot" else int(control_type),
                                            dtype=torch.int32, device=dev)
             self.balance = balance if balance is not None else _lib.default_balance_params()
             self.gains = gains if gains is not None else default_balance_gains()
-            self.bal_records = torch.zeros((self.B, _lib.BAL_SIZE), **f64)
-            if not hasattr(self, "plan_in"):
-                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # caller writes rot_z here
-        self.policy = policy
-        if policy is not None:
-            if estimator is None:
-                self.sensors = torch.zeros((self.B, _lib.SN_SIZE), **f64)  # caller writes joints / IMU rate here
-            if command is None:
-                self.cmd = torch.zeros((self.B, _lib.CM_SIZE), **f64)      # caller writes the joystick velocities
-            self.policy_state = torch.zeros((self.B, policy_state_size()), **f64)  # zero = fresh
-            self.policy_out = torch.zeros((self.B, _lib.PY_SIZE), **f64)
-        self.plant = plant
         if plant is not None:
-            if not hasattr(self, "dt"):
-                if dt is None:
-                    raise ValueError("ControlTick(plant=...) without plan= / estimator= / command= needs dt")
-                self.dt = float(dt)  # the plant's control period
-            if not hasattr(self, "plan_in"):
-                self.plan_in = torch.zeros((self.B, _lib.PL_SIZE), **f64)  # the foot forces are written here
-            self.plant_state = torch.zeros((self.B, plant_state_size()), **f64)  # zero = fresh
-            self.plant_out = torch.zeros((self.B, _lib.PT_SIZE), **f64)
             self.plant_init = None
             if plant_init is not None:
-                rows = torch.as_tensor(plant_init, dtype=torch.float64).reshape(self.B, _lib.PI_SIZE)
-                self.plant_init = rows.to(dev).contiguous()
-        self.episode = None
+                self.plant_init = given(plant_init).reshape(self.B, _lib.PI_SIZE).to(dev).contiguous()
+        self.episode = self.disturb = None
         if episode is not None:
-            if plant is None or episode_pool is None:
-                raise ValueError("ControlTick(episode=...) needs plant= and episode_pool=")
-            pool = torch.as_tensor(episode_pool, dtype=torch.float64).reshape(-1, POOL_SIZE)
+            self.episode_pool = given(episode_pool).reshape(-1, POOL_SIZE).to(dev).contiguous()
             ep = EpisodeParams.from_buffer_copy(episode)
-            ep.dt, ep.pool_count, ep.log_len = self.dt, pool.shape[0], int(episode_log_len)
+            ep.dt, ep.pool_count, ep.log_len = self.dt, self.episode_pool.shape[0], int(episode_log_len)
             ep.script_count = ep.script_segments = 0
-            self.episode_pool = pool.to(dev).contiguous()
             self.episode_scripts = None
             if episode_scripts is not None:
-                sc = torch.as_tensor(episode_scripts, dtype=torch.float64)
+                sc = given(episode_scripts)
                 sc = sc.reshape(sc.shape[0], -1, SEG_SIZE)
                 ep.script_count, ep.script_segments = sc.shape[0], sc.shape[1]
                 self.episode_scripts = sc.to(dev).contiguous()
             if self.plant_init is None:
                 self.plant_init = self.episode_pool[:1, POOL_INIT:POOL_INIT + _lib.PI_SIZE].repeat(self.B, 1)
-            self.episode_state = torch.zeros((self.B, episode_state_size()), **f64)  # zero = fresh
-            self.episode_log = torch.zeros((self.B, ep.log_len, EL_SIZE), **f64)
-            self.episode_totals = torch.zeros((self.B, ET_SIZE), **f64)
-            ptr = lambda name: getattr(self, name).data_ptr() if getattr(self, name, None) is not None else 0
-            size = lambda name: getattr(self, name).shape[1] if hasattr(self, name) else 0
-            self.episode_buffers = episode_buffers(
-                ptr("plant_out"), ptr("plant_state"), ptr("plant_init"), ptr("torques"), ptr("sensors"), ptr("cmd"),
-                ptr("results"), ptr("episode_pool"), ptr("episode_scripts"), ptr("states"), ptr("counter"),
-                ptr("episode_log"), ptr("episode_totals"), ptr("est_state"), size("est_state"), ptr("plan_state"),
-                size("plan_state"), ptr("cmd_state"), size("cmd_state"), ptr("policy_state"), size("policy_state"),
-                ptr("warm"), size("warm"))
-            self.episode = ep
-        self.disturb = None
+            self.episode = o["episode"] = ep
         if disturb is not None:
-            if plant is None or self.episode is None:
-                raise ValueError("ControlTick(disturb=...) needs plant= and episode=")
             dp = DisturbParams.from_buffer_copy(disturb)
             self.disturb_dirs = None
             dp.dir_count = 0
             if disturb_dirs is not None:
-                dirs = torch.as_tensor(disturb_dirs, dtype=torch.float64).reshape(-1, 4)
-                dp.dir_count = dirs.shape[0]
-                self.disturb_dirs = dirs.to(dev).contiguous()
-            self.wrench = torch.zeros((self.B, PW_SIZE), **f64)
-            self.disturb_out = torch.zeros((self.B, DO_SIZE), **f64)
-            if hasattr(self, "sensors"):
-                self.sensors_noisy = torch.zeros((self.B, _lib.SN_SIZE), **f64)
-            ptr = lambda name: getattr(self, name).data_ptr() if getattr(self, name, None) is not None else 0
-            self.disturb_buffers = disturb_buffers(ptr("episode_state"), ptr("wrench"), ptr("sensors"),
-                                                   ptr("sensors_noisy"), ptr("disturb_dirs"), ptr("disturb_out"))
-            self.disturb = dp
+                self.disturb_dirs = given(disturb_dirs).reshape(-1, 4).to(dev).contiguous()
+                dp.dir_count = self.disturb_dirs.shape[0]
+            self.disturb = o["disturb"] = dp
+        self.counter = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        for name, width in self._buffers(o).items():  # zero = a fresh slot, an uninitialised filter, a reset controller
+            if width is not None:
+                setattr(self, name, torch.zeros((self.B, *width) if isinstance(width, tuple) else (self.B, width),
+                                                dtype=torch.float64, device=dev))
+        self._options, self._dt_arg = o, dt
+        self._tick = self._stage_list(o, tick_dt)
+        if self.episode is not None:
+            self.episode_buffers = self._episode_buffers(o)
+        if self.disturb is not None:
+            self.disturb_buffers = self._disturb_buffers(o)
         self.graph = None
+
+    @staticmethod
+    def _check(o, dt, pool):
+        """Reject the combinations of options the constructor rejects.  Returns the tick's dt: the argument of
+        update_plan, update_estimation and main_update and the plant's control period (None: no stage takes one)."""
+        on = lambda name: o[name] is not None
+        ct = o["control_type"]
+        if on("plan"):
+            dt = o["plan"].control_dt if dt is None else dt
+        for name in ("estimator", "command"):
+            if on(name) and dt is None:
+                raise ValueError(f"ControlTick({name}=...) without plan= needs dt")
+        if ct not in (None, 0, 1, "per_robot") and not (ct == 2 and on("policy")):
+            raise ValueError('control_type must be None, 0, 1 or "per_robot" (or 2 with policy=)')
+        if on("policy") and ct not in ("per_robot", 2):
+            raise ValueError('ControlTick(policy=...) needs control_type="per_robot" or 2')
+        if on("plant") and dt is None:
+            raise ValueError("ControlTick(plant=...) without plan= / estimator= / command= needs dt")
+        if on("episode") and (not on("plant") or pool is None):
+            raise ValueError("ControlTick(episode=...) needs plant= and episode_pool=")
+        if on("disturb") and not (on("plant") and on("episode")):
+            raise ValueError("ControlTick(disturb=...) needs plant= and episode=")
+        return float(dt) if on("plan") or on("estimator") or on("command") or on("plant") else None
+
+    def _buffers(self, o):
+        """name -> row width in doubles of every buffer a tick with the options `o` owns.  A width is an int or,
+        for rows of more than one dimension, a tuple; None marks a buffer that is not a zero-filled float64
+        [B, width] tensor: the constructor builds it from an argument, and it may be None."""
+        on = {name for name, v in o.items() if v is not None}
+        sensors = on & {"estimator", "policy"}  # the estimator's input, else the policy stage's (caller-written)
+        t = dict(states=_lib.ST_SIZE,        # caller writes robot states here
+                 tq_records=_lib.TQ_SIZE,    # and Jacobians / swing forces here
+                 records=_lib.rec_size(self.solver.horizon), warm=self.solver.warm_state_size,
+                 results=_lib.RESULT_DOUBLES, torques=12, counter=None)
+        if "plan" in on:
+            t.update(plan_state=plan_state_size(), plan_out=_lib.PO_SIZE)
+        if on & {"plan", "estimator", "command", "control_type", "plant"}:
+            t["plan_in"] = _lib.PL_SIZE      # rot_z / foot_force / movement_mode, whichever the stages leave the caller
+        if "estimator" in on:
+            t.update(est_state=estimator_state_size(), est_out=_lib.EO_SIZE)
+        if sensors:
+            t["sensors"] = _lib.SN_SIZE      # quat / joints / IMU: the caller's, or the plant's
+        if "command" in on:
+            t["cmd_state"] = command_state_size()
+        if on & {"command", "policy"}:
+            t["cmd"] = _lib.CM_SIZE          # caller writes joystick-level commands here
+        if "control_type" in on:
+            t.update(control_type=None, bal_records=_lib.BAL_SIZE)
+        if "policy" in on:
+            t.update(policy_state=policy_state_size(), policy_out=_lib.PY_SIZE)
+        if "plant" in on:
+            t.update(plant_state=plant_state_size(), plant_out=_lib.PT_SIZE, plant_init=None)
+        if "episode" in on:
+            t.update(episode_state=episode_state_size(), episode_log=(o["episode"].log_len, EL_SIZE),
+                     episode_totals=ET_SIZE, episode_pool=None, episode_scripts=None)
+        if "disturb" in on:
+            t.update(wrench=PW_SIZE, disturb_out=DO_SIZE, disturb_dirs=None)
+            if sensors:
+                t["sensors_noisy"] = _lib.SN_SIZE
+        return t
+
+    def _ptr(self, o):
+        """ptr(name): the device pointer of a buffer the tick of the options `o` owns, else 0."""
+        own = self._buffers(o)
+
+        def ptr(name):
+            t = getattr(self, name) if name in own else None
+            return t.data_ptr() if t is not None else 0
+        return ptr
+
+    def _episode_buffers(self, o):
+        p, w = self._ptr(o), self._buffers(o)
+        return episode_buffers(
+            p("plant_out"), p("plant_state"), p("plant_init"), p("torques"), p("sensors"), p("cmd"), p("results"),
+            p("episode_pool"), p("episode_scripts"), p("states"), p("counter"), p("episode_log"), p("episode_totals"),
+            p("est_state"), w.get("est_state", 0), p("plan_state"), w.get("plan_state", 0), p("cmd_state"),
+            w.get("cmd_state", 0), p("policy_state"), w.get("policy_state", 0), p("warm"), w["warm"])
+
+    def _disturb_buffers(self, o):
+        p = self._ptr(o)
+        return disturb_buffers(p("episode_state"), p("wrench"), p("sensors"), p("sensors_noisy"), p("disturb_dirs"),
+                               p("disturb_out"))
+
+    def _stage_list(self, o, dt):
+        """The tick of the options `o` on this tick's buffers: its ordered (name, enqueue(stream)) pairs.  The
+        untyped tick passes a null type pointer to the typed plan and warm solve, which is what
+        mpcqp_leg_plan_device and mpcqp_solve_batch_warm_device do themselves."""
+        on = lambda name: o[name] is not None
+        p, B, solver = self._ptr(o), self.B, self.solver
+        sensed = "sensors_noisy" if on("disturb") else "sensors"  # the row the controller's stages read
+        truth = not on("estimator")  # the plant then also writes what the estimator would
+        st = []
+        if on("disturb"):
+            dbf = self._disturb_buffers(o)
+            st.append(("disturb", lambda s: disturb_device(o["disturb"], dbf, B, s)))
+        if on("command"):
+            st.append(("command", lambda s: command_device(
+                o["command"], dt, p("cmd"), p("states"), p("plan_in"), B, p("cmd_state"), s)))
+        if on("estimator"):
+            st.append(("estimate", lambda s: state_estimate_device(
+                o["estimator"], dt, p(sensed), p("plan_in"), p("states"), B, p("est_state"), p("tq_records"),
+                p("est_out"), s)))
+        if on("plan"):
+            st.append(("plan", lambda s: leg_plan_typed_device(
+                o["plan"], dt, p("states"), p("plan_in"), B, p("plan_state"), p("tq_records"), p("plan_out"),
+                p("control_type"), s)))
+        st.append(("assemble", lambda s: _lib.assemble_records_device(
+            solver.horizon, p("states"), B, p("records"), s)))
+        if on("control_type"):
+            st.append(("assemble_balance", lambda s: assemble_balance_device(
+                self.gains, p("states"), p("plan_in"), p("cmd_state"), B, p("bal_records"), s)))
+            st.append(("balance", lambda s: solver.balance_solve_typed_device(
+                self.balance, p("bal_records"), B, p("control_type"), 0, p("results"), s)))
+        st.append(("solve", lambda s: solver.solve_warm_typed_device(
+            p("records"), B, p("warm"), p("control_type"), 1, p("results"), 0, s)))
+        st.append(("torques", lambda s: joint_torques_device(
+            p("tq_records"), p("results"), B, p("counter"), p("torques"), s)))
+        if on("policy"):
+            st.append(("policy", lambda s: policy_device(
+                o["policy"], p(sensed), p("states"), p("plan_in"), p("cmd"), B, p("policy_state"), p("torques"),
+                p("policy_out"), p("control_type"), 2, s)))
+        if on("plant"):
+            rows = lambda s: (B, p("plant_state"), p("plant_init"), p("sensors"), p("plan_in"),
+                              p("states") if truth else 0, p("tq_records") if truth else 0, p("plant_out"), s)
+            if on("disturb"):
+                st.append(("plant", lambda s: plant_step_wrench_device(
+                    o["plant"], dt, p("torques"), p("wrench"), *rows(s))))
+            else:
+                st.append(("plant", lambda s: plant_step_device(o["plant"], dt, p("torques"), *rows(s))))
+        if on("episode"):
+            ebf = self._episode_buffers(o)
+            st.append(("episode", lambda s: episode_device(o["episode"], ebf, B, p("episode_state"), s)))
+        return st
+
+    def _stages_of(self, without):
+        """This tick's stage list, or the one the constructor would have built, on the same buffers, had the
+        options of the stages `without` been None (a constructor option's own name is accepted as well)."""
+        if not without:
+            return self._tick
+        o = dict(self._options)
+        for name in without:
+            option = _OPTION_OF.get(name, name)
+            if option not in o:
+                raise ValueError(f"ControlTick: {name!r} is not a stage that can be left out "
+                                 f"(one of {', '.join(_OPTION_OF)})")
+            o[option] = None
+        return self._stage_list(o, self._check(o, self._dt_arg, getattr(self, "episode_pool", None)))
+
+    def _stream(self, stream):
+        return stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
+
+    def _enqueue(self, name, stream):
+        dict(self._tick)[name](self._stream(stream))
+
+    def stages(self, without=()):
+        """The names of the tick's stages in the order they are enqueued; ``without`` as in ``capture``."""
+        return tuple(name for name, _ in self._stages_of(without))
+
+    def _step(self, stages, stream, episode):
+        s = self._stream(stream)
+        for name, enqueue in stages:
+            if episode or name != "episode":
+                enqueue(s)
 
     def step(self, stream=None, episode=True):
         """Enqueue one tick on `stream` (default: torch's current stream).  ``episode=False`` leaves the episode
         stage out, for a caller that reads the tick's rows before enqueueing it with ``episode_stage()``."""
-        s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
-        if self.disturb is not None:
-            self.disturb_stage(s)
-        if self.command is not None:
-            command_device(self.command, self.dt, self.cmd.data_ptr(), self.states.data_ptr(),
-                           self.plan_in.data_ptr(), self.B, self.cmd_state.data_ptr(), s)
-        if self.estimator is not None:
-            state_estimate_device(self.estimator, self.dt, self._sensed().data_ptr(), self.plan_in.data_ptr(),
-                                  self.states.data_ptr(), self.B, self.est_state.data_ptr(),
-                                  self.tq_records.data_ptr(), self.est_out.data_ptr(), s)
-        if self.typed:
-            return self._step_typed(s, episode)
-        if self.plan is not None:
-            leg_plan_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
-                            self.plan_state.data_ptr(), self.tq_records.data_ptr(), self.plan_out.data_ptr(), s)
-        _lib.assemble_records_device(self.solver.horizon, self.states.data_ptr(), self.B, self.records.data_ptr(), s)
-        self.solver.solve_warm_device(self.records.data_ptr(), self.B, self.warm.data_ptr(), self.results.data_ptr(),
-                                      0, s)
-        joint_torques_device(self.tq_records.data_ptr(), self.results.data_ptr(), self.B, self.counter.data_ptr(),
-                             self.torques.data_ptr(), s)
-        if self.plant is not None:
-            self._step_plant(s)
-        if self.episode is not None and episode:
-            self.episode_stage(s)
+        self._step(self._tick, stream, episode)
 
     def disturb_stage(self, stream=None):
         """Enqueue the disturbance stage alone: first in the tick (``disturb_buffers``)."""
-        s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
-        disturb_device(self.disturb, self.disturb_buffers, self.B, s)
-
-    def _sensed(self):
-        """The sensor row the controller's stages read: the noisy one with the disturbance stage."""
-        return self.sensors_noisy if self.disturb is not None else self.sensors
+        self._enqueue("disturb", stream)
 
     def episode_stage(self, stream=None):
         """Enqueue the episode stage alone: last in the tick, on whichever of the sensors, cmd and slot buffers
         the tick has (``episode_buffers``)."""
-        s = stream if stream is not None else self.torch.cuda.current_stream().cuda_stream
-        episode_device(self.episode, self.episode_buffers, self.B, self.episode_state.data_ptr(), s)
-
-    def _step_plant(self, s):
-        """The plant stage, last in the tick: the final ``torques`` row moves every robot one control period on.
-        With the estimator it writes what sensors would deliver; without it, also the truth image of what the
-        estimator would write."""
-        truth = self.estimator is None
-        rows = (self.B, self.plant_state.data_ptr(), self.plant_init.data_ptr() if self.plant_init is not None else 0,
-                self.sensors.data_ptr() if hasattr(self, "sensors") else 0, self.plan_in.data_ptr(),
-                self.states.data_ptr() if truth else 0, self.tq_records.data_ptr() if truth else 0,
-                self.plant_out.data_ptr(), s)
-        if self.disturb is not None:
-            plant_step_wrench_device(self.plant, self.dt, self.torques.data_ptr(), self.wrench.data_ptr(), *rows)
-        else:
-            plant_step_device(self.plant, self.dt, self.torques.data_ptr(), *rows)
+        self._enqueue("episode", stream)
 
     def prime_plant(self, stream=None):
         """Enqueue the plant stage alone.  On fresh slots (after construction or a reset) it initialises them from
         ``plant_init`` and writes the rows of the start without integrating, so the first tick's estimator, plan
         and solve see the robot where it stands instead of zero rows.  (On a slot that is not fresh it is one
         more step under the current ``torques``.)"""
-        self._step_plant(stream if stream is not None else self.torch.cuda.current_stream().cuda_stream)
+        self._enqueue("plant", stream)
 
-    def _step_typed(self, s, episode=True):
-        """plan -> both assemblies -> balance solve of the type-0 robots -> warm MPC solve of the type-1
-        robots -> torque map -> policy stage of the type-2 robots; every kernel reads ``control_type`` when it
-        runs."""
-        ty = self.control_type.data_ptr()
-        if self.plan is not None:
-            leg_plan_typed_device(self.plan, self.dt, self.states.data_ptr(), self.plan_in.data_ptr(), self.B,
-                                  self.plan_state.data_ptr(), self.tq_records.data_ptr(), self.plan_out.data_ptr(),
-                                  ty, s)
-        _lib.assemble_records_device(self.solver.horizon, self.states.data_ptr(), self.B, self.records.data_ptr(), s)
-        assemble_balance_device(self.gains, self.states.data_ptr(), self.plan_in.data_ptr(),
-                                self.cmd_state.data_ptr() if self.command is not None else 0, self.B,
-                                self.bal_records.data_ptr(), s)
-        self.solver.balance_solve_typed_device(self.balance, self.bal_records.data_ptr(), self.B, ty, 0,
-                                               self.results.data_ptr(), s)
-        self.solver.solve_warm_typed_device(self.records.data_ptr(), self.B, self.warm.data_ptr(), ty, 1,
-                                            self.results.data_ptr(), 0, s)
-        joint_torques_device(self.tq_records.data_ptr(), self.results.data_ptr(), self.B, self.counter.data_ptr(),
-                             self.torques.data_ptr(), s)
-        if self.policy is not None:
-            policy_device(self.policy, self._sensed().data_ptr(), self.states.data_ptr(), self.plan_in.data_ptr(),
-                          self.cmd.data_ptr(), self.B, self.policy_state.data_ptr(), self.torques.data_ptr(),
-                          self.policy_out.data_ptr(), ty, 2, s)
-        if self.plant is not None:
-            self._step_plant(s)
-        if self.episode is not None and episode:
-            self.episode_stage(s)
-
-    def capture(self):
+    def capture(self, without=()):
         """Record step() as a graph.  Estimator, plan and warm slots, counters and torques keep evolving on replay,
         exactly as with eager steps; capture itself launches nothing.  The estimator and plan parameters and dt are
-        kernel arguments, so the graph keeps the values they had at capture."""
+        kernel arguments, so the graph keeps the values they had at capture.
+        ``without`` (stage names) records instead the tick the constructor would have built had those stages'
+        options been None, on the same buffers: without ``disturb`` the estimator and the policy stage read
+        ``sensors`` and the plant runs without the wrench row; without ``estimate`` the plant also writes the
+        truth image.  A combination the constructor rejects raises its ValueError (``plant`` under an episode
+        stage).  Only the full tick's graph becomes ``self.graph``."""
         torch = self.torch
+        stages = self._stages_of(without)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.step()
-        self.graph = g
+            self._step(stages, None, True)
+        if not without:
+            self.graph = g
         return g
 
     def replay(self):

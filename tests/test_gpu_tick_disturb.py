@@ -262,7 +262,7 @@ def test_a_push_moves_the_trunk_in_the_predicted_tick():
 
 # ---- 5. the per-robot tick with the policy stage ----
 def test_typed_tick_with_the_policy_reads_the_noisy_row():
-    """The tick with a control type per robot (balance QP, MPC and the policy stage) takes the other step path: its
+    """The tick with a control type per robot (balance QP, MPC and the policy stage) has the longest stage list: its
     eager steps and its graph's replays agree bitwise, and the noise reaches the policy stage: the policy's output
     row is that of the same tick without noise until the first running tick, and differs from it there."""
     import policy_reference as ref

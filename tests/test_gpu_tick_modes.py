@@ -53,7 +53,8 @@ def _make():
 
 
 def _staged(k):
-    """ControlTick._step_typed's stages, one entry point at a time on the object's buffers."""
+    """The stages ControlTick.step walks for the tick with a control type, one entry point at a time on the
+    object's buffers."""
     s = torch.cuda.current_stream().cuda_stream
     ty = k.control_type.data_ptr()
     mpcqp.command_device(k.command, k.dt, k.cmd.data_ptr(), k.states.data_ptr(), k.plan_in.data_ptr(), B,

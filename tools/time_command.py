@@ -40,6 +40,29 @@ def spread(times):
     return {"median_ms": statistics.median(t), "min_ms": t[0], "q1_ms": q[0], "q3_ms": q[2], "max_ms": t[-1]}
 
 
+def paired_tick_ms(k, without, settle):
+    """The graph-replayed tick `k` with and without the stages `without` (ControlTick.capture(without=): the same
+    tick on the same buffers).  After `settle` replays of the full graph, each of WARMUP + RUNS repetitions
+    snapshots every tensor of the tick, replays the graph without, restores the snapshot and replays the full one,
+    so the two replays of a pair do the same work from the same slots but for the stages (the solver handle's
+    launch-order hint is the one state not restored).  Returns the spread of the full tick's times, of the times
+    without, and the median and extremes of the paired differences."""
+    g_with, g_without = k.capture(), k.capture(without=without)
+    for _ in range(settle):
+        g_with.replay()
+    tensors = [v for v in vars(k).values() if isinstance(v, torch.Tensor)]
+    t_with, t_without, diff = [], [], []
+    for _ in range(WARMUP + RUNS):
+        snap = [t.clone() for t in tensors]
+        t_without.append(event_ms(g_without.replay))
+        for t, c in zip(tensors, snap):
+            t.copy_(c)
+        t_with.append(event_ms(g_with.replay))
+        diff.append(t_with[-1] - t_without[-1])
+    d = sorted(diff[WARMUP:])
+    return spread(t_with), spread(t_without), {"median_ms": d[len(d) // 2], "min_ms": d[0], "max_ms": d[-1]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)

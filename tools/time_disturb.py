@@ -33,8 +33,8 @@ from mpcqp import disturb as md  # noqa: E402
 from mpcqp import episode as me  # noqa: E402
 from mpcqp.tick import ControlTick  # noqa: E402
 from rollout import DT, caller_rows, episode_pool, full_stance  # noqa: E402
-from time_command import spread  # noqa: E402
-from time_estimator import RUNS, WARMUP, event_ms, median_ms  # noqa: E402
+from time_command import paired_tick_ms  # noqa: E402
+from time_estimator import RUNS, WARMUP, median_ms  # noqa: E402
 
 
 def all_on(**over):
@@ -49,7 +49,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
     B = ap.parse_args().batch
-    T = WARMUP + RUNS
     f64 = dict(dtype=torch.float64, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     out = {"batch": B, "warmup": WARMUP, "runs": RUNS}
@@ -131,24 +130,11 @@ def main():
                         episode_pool=episode_pool(8, q, 0.05, 2, h), disturb=all_on(push_interval=200, push_duration=20),
                         disturb_dirs=mpcqp.pack_push_dirs(16), **kw)
         caller_rows(k, B, np.zeros((B, 3)), np.zeros(B), full)
-        g_with = k.capture()
-        stage, k.disturb = k.disturb, None  # the same tick on the same buffers without its first stage
-        g_without = k.capture()
-        k.disturb, k.graph = stage, g_with
-        for _ in range(14):  # the fresh and the priming tick, then past the torque map's zero-torque ticks
-            g_with.replay()
-        tensors = [v for v in vars(k).values() if isinstance(v, torch.Tensor)]
-        t_with, t_without, diff = [], [], []
-        for _ in range(T):
-            snap = [t.clone() for t in tensors]
-            t_without.append(event_ms(g_without.replay))
-            for t, c in zip(tensors, snap):
-                t.copy_(c)
-            t_with.append(event_ms(g_with.replay))
-            diff.append(t_with[-1] - t_without[-1])
-        k.close()
-        d = sorted(diff[WARMUP:])
-        return spread(t_with), spread(t_without), {"median_ms": d[len(d) // 2], "min_ms": d[0], "max_ms": d[-1]}
+        try:
+            # the fresh and the priming tick, then past the torque map\'s zero-torque ticks
+            return paired_tick_ms(k, ("disturb",), 14)
+        finally:
+            k.close()
 
     for name, full in (("mpc", False), ("full", True)):
         w, wo, d = pair(full)

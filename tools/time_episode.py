@@ -29,8 +29,8 @@ from mpcqp import _lib  # noqa: E402
 from mpcqp import episode as me  # noqa: E402
 from mpcqp.tick import ControlTick  # noqa: E402
 from rollout import DT, caller_rows, episode_pool, full_stance  # noqa: E402
-from time_command import spread  # noqa: E402
-from time_estimator import RUNS, WARMUP, event_ms, median_ms  # noqa: E402
+from time_command import paired_tick_ms  # noqa: E402
+from time_estimator import RUNS, WARMUP, median_ms  # noqa: E402
 
 
 def main():
@@ -121,24 +121,11 @@ def main():
         k = ControlTick(B, dt=DT, plant=mpcqp.default_plant_params(), episode=mpcqp.default_episode_params(seed=5),
                         episode_pool=episode_pool(8, q, 0.05, 2, h), **kw)
         caller_rows(k, B, np.zeros((B, 3)), np.zeros(B), full)
-        g_with = k.capture()
-        episode, k.episode = k.episode, None  # the same tick on the same buffers without its last stage
-        g_without = k.capture()
-        k.episode, k.graph = episode, g_with
-        for _ in range(14):  # the fresh and the priming tick, then past the torque map's zero-torque ticks
-            g_with.replay()
-        tensors = [v for v in vars(k).values() if isinstance(v, torch.Tensor)]
-        t_with, t_without, diff = [], [], []
-        for _ in range(T):
-            snap = [t.clone() for t in tensors]
-            t_without.append(event_ms(g_without.replay))
-            for t, c in zip(tensors, snap):
-                t.copy_(c)
-            t_with.append(event_ms(g_with.replay))
-            diff.append(t_with[-1] - t_without[-1])
-        k.close()
-        d = sorted(diff[WARMUP:])
-        return spread(t_with), spread(t_without), {"median_ms": d[len(d) // 2], "min_ms": d[0], "max_ms": d[-1]}
+        try:
+            # the fresh and the priming tick, then past the torque map\'s zero-torque ticks
+            return paired_tick_ms(k, ("episode",), 14)
+        finally:
+            k.close()
 
     for name, full in (("mpc", False), ("full", True)):
         w, wo, d = pair(full)

@@ -31,15 +31,14 @@ from mpcqp import _lib  # noqa: E402
 from mpcqp.tick import ControlTick  # noqa: E402
 from rollout import DT, caller_rows, start_rows  # noqa: E402
 from test_torques import torque_inputs  # noqa: E402  (synthetic Jacobians)
-from time_command import spread  # noqa: E402
-from time_estimator import RUNS, WARMUP, event_ms, median_ms  # noqa: E402
+from time_command import paired_tick_ms  # noqa: E402
+from time_estimator import RUNS, WARMUP, median_ms  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
     B = ap.parse_args().batch
-    T = WARMUP + RUNS
     f64 = dict(dtype=torch.float64, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     out = {"batch": B, "warmup": WARMUP, "runs": RUNS}
@@ -105,24 +104,10 @@ def main():
         k = ControlTick(B, dt=DT, plant=mpcqp.default_plant_params(), plant_init=init, **kw)
         caller_rows(k, B, init[:, :3], e[:, 2], full)
         k.prime_plant()
-        g_with = k.capture()
-        plant, k.plant = k.plant, None  # the same tick on the same buffers without its last stage
-        g_without = k.capture()
-        k.plant, k.graph = plant, g_with
-        for _ in range(12):  # past the torque map's zero-torque ticks
-            g_with.replay()
-        tensors = [v for v in vars(k).values() if isinstance(v, torch.Tensor)]
-        t_with, t_without, diff = [], [], []
-        for _ in range(T):
-            snap = [t.clone() for t in tensors]
-            t_without.append(event_ms(g_without.replay))
-            for t, c in zip(tensors, snap):
-                t.copy_(c)
-            t_with.append(event_ms(g_with.replay))
-            diff.append(t_with[-1] - t_without[-1])
-        k.close()
-        d = sorted(diff[WARMUP:])
-        return spread(t_with), spread(t_without), {"median_ms": d[len(d) // 2], "min_ms": d[0], "max_ms": d[-1]}
+        try:
+            return paired_tick_ms(k, ("plant",), 12)  # past the torque map's zero-torque ticks
+        finally:
+            k.close()
 
     for name, full in (("mpc", False), ("full", True)):
         w, wo, d = pair(full)
