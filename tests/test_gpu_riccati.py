@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import mpcqp
-from gpu_helpers import build_qp_gpu, rel_err_u0, solve_gpu
+from gpu_helpers import build_qp_gpu, note, rel_err_u0, sentinel, solve_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -26,8 +26,11 @@ def _oracle_params(oracle, p):
         eps_abs=p.eps_abs, eps_rel=p.eps_rel, adaptive_rho_interval=p.adaptive_rho_interval)
 
 
-def _check_p1_riccati(oracle, solver, recs, label, min_iter_equal=0.99):
-    op = _oracle_params(oracle, solver.params)
+def _check_p1_riccati(oracle, solver, recs, label, min_iter_equal=0.99, sent=None, oracle_params=None):
+    """oracle_params: the oracle's parameters where they are not the handle's own (a handle that carries the
+    gravity-weight lever of tests/test_riccati_lever.py is compared with the oracle's default-weight run).
+    sent: a regression sentinel on the u0 error; it and the equal-iteration fraction go to the sentinel log."""
+    op = _oracle_params(oracle, solver.params) if oracle_params is None else oracle_params
     ref, ref_sol = oracle.solve_batch(op, recs, nthreads=8, want_solution=True)
     got, sol, _ = solve_gpu(solver, recs)
     err = rel_err_u0(got["u0"], ref["u0"])
@@ -41,6 +44,14 @@ def _check_p1_riccati(oracle, solver, recs, label, min_iter_equal=0.99):
     assert np.mean(di == 0) >= min_iter_equal, f"{label}: only {np.mean(di == 0):.2f} identical iteration counts"
     fb = np.max(np.abs(got["f_body"] - ref["f_body"]), axis=1) / np.maximum(np.max(np.abs(ref["f_body"]), axis=1), 1)
     assert np.all(fb <= TOL_P1), label
+    full = np.max(np.abs(sol - ref_sol), axis=1) / np.maximum(np.max(np.abs(ref_sol), axis=1), 1)
+    assert np.all(full <= TOL_P1), f"{label}: full-horizon solution worst {full.max()}"
+    same = di == 0
+    np.testing.assert_array_equal(got["rho_updates"][same], ref["rho_updates"][same], err_msg=label)
+    if sent is not None:
+        note(f"riccati {label}", iter_equal_fraction=float(np.mean(same)), batch=int(di.size),
+             max_iter_drift=int(di.max()), max_rel_err_solution=float(full.max()))
+        sentinel(err, sent, f"riccati {label}")
     return got, ref, err
 
 
@@ -78,7 +89,8 @@ def test_n20_test_mpc_case(oracle):
         _check_p1_riccati(oracle, s, rec[None], "test_mpc N=20", min_iter_equal=1.0)
 
 
-def test_n20_edge_cases(oracle, n20_solver):
+def _edge_states():
+    """Eight robots: 0 all swing, 1 all stance, 2 / 3 yaw +-pi, 4 fz pinned at its bound, 5 heavy."""
     st = mpcqp.synthetic_go1(8, seed=4, gait="stance")
     st.contacts[0] = False
     st.contacts[1] = True
@@ -87,7 +99,11 @@ def test_n20_edge_cases(oracle, n20_solver):
     st.root_pos_d[4, 2] = 5.0
     st.robot_mass = np.full(8, 13.0)
     st.robot_mass[5] = 40.0
-    recs = mpcqp.assemble_compute_grf(st, 20)
+    return st
+
+
+def test_n20_edge_cases(oracle, n20_solver):
+    recs = mpcqp.assemble_compute_grf(_edge_states(), 20)
     got, _, _ = _check_p1_riccati(oracle, n20_solver, recs, "edge N=20", min_iter_equal=0.75)
     assert np.all(np.abs(got["u0"][0]) <= 1e-6), "all-swing robot must get zero forces"
 
@@ -102,7 +118,9 @@ def test_intermediate_horizons(oracle, N):
 
 @pytest.mark.parametrize("N", [1, 10])
 def test_forced_riccati_small_horizons(oracle, N):
-    """The Riccati path on horizons the dense path serves: cross-check both against the oracle."""
+    """The debug library's workgroup Riccati kernel (csrc/mpcqp_riccati.hip, SOLVER_RICCATI) on horizons its
+    dense kernel serves: both cross-check solvers against the oracle.  This is not the product's wave kernel:
+    wave_kernel<N, 0> at these horizons is covered by tests/test_gpu_riccati_horizons.py."""
     st = mpcqp.synthetic_go1(64, seed=400 + N, gait="mixed", mixed_mu=True)
     recs = mpcqp.assemble_compute_grf(st, N)
     with mpcqp.MpcQpSolver(mpcqp.default_params(N), debug=True) as s:
