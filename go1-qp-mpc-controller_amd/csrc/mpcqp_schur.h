@@ -17,17 +17,23 @@
 // eigenvalues >= 1, condition ~1e0-1e3 on the Go1 workload):
 //   (c B6'M B6 + R')^-1 w = R'^-1 w - B' (I - S^-1) B w,   B := Li B6 R'^-1  (6N x 12N, per step 6x12)
 // (push-through identity; exact in real arithmetic).  Per factorization (rho change): R'^-1 per
-// foot, B (per step), S (6N x 6N) and Q = I - S^-1 by a blocked Gauss-Jordan sweep (schur_gj_mfma).  Per ADMM
+// foot, B (per step), S (6N x 6N) and Q = I - S^-1 by a blocked Gauss-Jordan sweep (schur_gj_tiles).  Per ADMM
 // iteration:  z = B w (6x12 per step),  q = Q z (dense, one lane per row of Q),  u = R'^-1 w - B' q.
+// From three block rows up (N >= 6, SchurCfg::TILED) S is formed directly as the sweep's upper 16x16
+// tiles from a table of the lanes' V, W columns in the factorization scratch (schur_build_tiles) and the
+// prologue's rows of B6 R'^-1 read their operands in one batch; below that S is formed by rows and cut
+// into tiles with permutes (schur_build_rows, schur_gj_mfma).  Both give the same bits.
 //
 // Lane roles inside the one wave of a robot: the ADMM layout of wave_kernel (variable lanes: step
 // 4r + gray(q) of round r in DPP row q, lane 4 leg + a) and, for the dense part, one lane per impulse
 // unknown i = 6 k + c (step k, component c: omega_x,y,z, v_x,y,z), i < 6N <= 60.  The two meet
 // through LDS (w out, q back), in order within the wave.
 #pragma once
+#include <stddef.h>
+
 #include "mpcqp_wave_common.h"
 
-// 1 (default): Q = I - S^-1 by the blocked Gauss-Jordan sweep on the matrix cores (schur_gj_mfma);
+// 1 (default): Q = I - S^-1 by the blocked Gauss-Jordan sweep on the matrix cores (schur_gj_tiles);
 // 0: the in-register scalar sweep (schur_gj_valu).  Same box, 3 repetitions
 // (profiles/r06/gj_mfma/ab_final.txt): C2 1.549 -> 1.537 ms, C5 2.925 -> 2.901 ms; the sweep alone
 // 30.6k -> 27.1k cycles (tools/mb/mb_gjsweep).  Built with -mllvm -amdgpu-mfma-vgpr-form (Makefile):
@@ -49,6 +55,10 @@ struct SchurCfg {
   // first two, or a zero tail) only ever multiply pad unknowns, whose z is 0.
   static constexpr int QS = 62;
   static constexpr int BS = 14;  // row stride of B in LDS: 112 B, conflict-free b128 rows
+  // The factorization's batched prologue and tile-layout S build (schur_factor): from three block rows
+  // up.  Below that both are the earlier forms: there the new ones save little (S is one or two
+  // tiles) and the kernels' register counts came out 2 to 8 higher.
+  static constexpr bool TILED = N >= 6;
 };
 
 // Factorization scratch: lives in the rows of Q (which every factorization rewrites at its end).
@@ -351,12 +361,16 @@ struct GjPlanSym {
   static constexpr int count(int grp) { return -1 - list(grp, 1000); }
 };
 
-// S - I in the lane's row (lane t = row t, S[m] = column m; rows and columns NI..63 zero) -> Q in F.Q.
+// S - I in the lane's row (lane t = row t, S[m] = column m; rows and columns NI..63 zero) -> Q in F.Q:
+// the row-input front of the sweep (tools/mb/mb_gjsweep; schur_factor builds the tiles itself).
 // pre(): run after the sweep, before the first store to Q (the factorization scratch lives there);
 // mark(id): internal phase marks 60-64 (the caller records them after the sweep).
 template <int N, class Pre, class Mark>
+__device__ __forceinline__ void schur_gj_tiles(mf4 (&X)[(SchurCfg<N>::NI + 15) / 16][(SchurCfg<N>::NI + 15) / 16],
+                                               SchurLds<N>& F, int t, Pre&& pre, Mark&& mark);
+template <int N, class Pre, class Mark>
 __device__ __forceinline__ void schur_gj_mfma(const double (&S)[64], SchurLds<N>& F, int t, Pre&& pre, Mark&& mark) {
-  constexpr int NI = SchurCfg<N>::NI, QS = SchurCfg<N>::QS, NB = (NI + 15) / 16;
+  constexpr int NI = SchurCfg<N>::NI, NB = (NI + 15) / 16;
   const int j = t & 15, grp = t >> 4;
   mf4 X[NB][NB];
   // the upper tiles: X[I][J][v] in row g = S[16 I + 4 v + g] of lane 16 J + j, plus the identity
@@ -371,6 +385,14 @@ __device__ __forceinline__ void schur_gj_mfma(const double (&S)[64], SchurLds<N>
 #pragma unroll
       for (int J = I; J < NB; ++J) X[I][J][v] = y[J] + ((I == J && j == 4 * v + grp) ? 1.0 : 0.0);
     }
+  schur_gj_tiles<N>(X, F, t, pre, mark);
+}
+// The sweep proper: X[I][J], J >= I, the upper tiles of S (identity included) -> Q in F.Q.
+template <int N, class Pre, class Mark>
+__device__ __forceinline__ void schur_gj_tiles(mf4 (&X)[(SchurCfg<N>::NI + 15) / 16][(SchurCfg<N>::NI + 15) / 16],
+                                               SchurLds<N>& F, int t, Pre&& pre, Mark&& mark) {
+  constexpr int NI = SchurCfg<N>::NI, QS = SchurCfg<N>::QS, NB = (NI + 15) / 16;
+  const int j = t & 15, grp = t >> 4;
   mark(60);  // tiles made
   const mf4 zero = {0.0, 0.0, 0.0, 0.0};
   // LDS staging above the live scratch (R'^-1): the pivot tile, then one buffer per transposed tile
@@ -592,6 +614,135 @@ __device__ __forceinline__ void schur_gj_valu(double (&S)[64], SchurLds<N>& F, i
   wave_sync();
 }
 
+// ---- S from its factors (schur_factor) ---------------------------------------------------------------
+// S - I = L'CL = beta o (V V') + alpha o (W W') (V, W: the 6-column halves of vw; beta, alpha per
+// step pair), row i in absolute column order, by row_newbcast dot products against four row
+// copies of each column: no LDS.  Entry (i, m) is the same fma chains by lanes i and m and the
+// same symmetric coefficients, so S is exactly symmetric.
+template <int N>
+__device__ __forceinline__ void schur_build_rows(const double (&vw)[12], int k, double (&S)[64]) {
+  constexpr int NI = SchurCfg<N>::NI;
+#pragma unroll
+  for (int m = 0; m < 64; ++m) S[m] = 0.0;
+  sfor<0, 2>([&](auto PART) __attribute__((always_inline)) {
+    constexpr int part = decltype(PART)::value;
+    double xc[4][6], v6[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+      v6[e] = vw[6 * part + e];
+      rowbcast4(v6[e], xc[0][e], xc[1][e], xc[2][e], xc[3][e]);
+    }
+    sfor<0, (NI + 3) / 4>([&](auto B) __attribute__((always_inline)) {
+      constexpr int m0 = 4 * decltype(B)::value, sr = m0 >> 4, l0 = m0 & 15;
+      double acc[4] = {0.0, 0.0, 0.0, 0.0};
+      dot6x4<(m0 & 15) == 0, l0, l0 + 1, l0 + 2, l0 + 3>(xc[sr], v6, acc[0], acc[1], acc[2], acc[3]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int m = m0 + j;
+        if (m < NI) {
+          const int l = m / 6;
+          if constexpr (part == 0) S[m] = (double)(N - (k > l ? k : l)) * acc[j];
+          else S[m] = fma(alpha_jl(N, k, l), acc[j], S[m]);
+        }
+      }
+    });
+  });
+  // S holds L'CL so far: the sweep adds the identity (schur_gj_valu: to each diagonal entry when its
+  // pivot comes, entry (j, j) being read first by pivot j; the MFMA forms: to the tiles) and pad rows
+  // stay 0.
+}
+
+#if MPCQP_GJ_MFMA
+// S = I + L'CL = I + beta o (V V') + alpha o (W W') (V, W: the 6-column halves of vw; beta, alpha
+// per step pair) directly as the sweep's tiles X[I][J], J >= I (schur_gj_tiles: register v of lane
+// j + 16 g holds S[16 I + 4 v + g][16 J + j]).  Entry (i, m) is the two fma chains over e of
+// vw_m[e] vw_i[e], from 0, then beta_kl times the first and alpha_kl times the second added by an
+// fma, as the row form has them (schur_gj_valu's input, below): the same bits, S exactly symmetric.
+// The operands come from a table in the factorization scratch, where B6R and G are no longer
+// needed (every lane holds its row of B and its column of L): row i = vw of lane i (pad lanes: 0),
+// TS doubles apart (112 B: conflict-free b128 rows, as BS), and behind it the (beta, alpha) pair of
+// every step pair, N pairs per row.  A lane reads its NB columns once and one row per register:
+// the rows of a DPP row's lanes are one address (a broadcast read).  No address depends on a read.
+// Against the row form (64 entries per lane, then 128 permutes to cut the tiles): the lower tiles'
+// FMAs, the permutes and the 128 VGPRs of a lane's row are gone (profiles/schur_factor/README.md).
+template <int N>
+__device__ __forceinline__ void schur_build_tiles(SchurScratch<N>& sc, const double (&vw)[12], int t, int k,
+                                                  mf4 (&X)[(SchurCfg<N>::NI + 15) / 16][(SchurCfg<N>::NI + 15) / 16]) {
+  constexpr int NI = SchurCfg<N>::NI;
+  constexpr int NB = (NI + 15) / 16, TS = 14;
+  static_assert(offsetof(SchurScratch<N>, B6R) / sizeof(double) + TS * 16 * NB + 2 * N * N <= NI * SchurCfg<N>::QS + 2,
+                "the S tables inside Q");
+  {
+    double* tab = &sc.B6R[0][0];
+    double* pt = tab + TS * 16 * NB;
+    wave_sync();
+    if (t < 16 * NB) {
+#pragma unroll
+      for (int e = 0; e < 12; e += 2) *reinterpret_cast<double2*>(&tab[TS * t + e]) = make_double2(vw[e], vw[e + 1]);
+    }
+#pragma unroll
+    for (int rr = 0; 64 * rr < N * N; ++rr) {
+      const int id = t + 64 * rr;
+      if (id < N * N) {
+        const int ka = id / N, kb = id % N;
+        *reinterpret_cast<double2*>(&pt[2 * id]) = make_double2((double)(N - (ka > kb ? ka : kb)), alpha_jl(N, ka, kb));
+      }
+    }
+    wave_sync();
+    const int j = t & 15, g = t >> 4;
+    // one batch: the lane's NB columns; 16 k of each: its offset in a row of the pair table
+    double cv[NB][12];
+    int kcs[NB];
+#pragma unroll
+    for (int J = 0; J < NB; ++J) {
+      const double* cp = tab + TS * (16 * J + j);
+#pragma unroll
+      for (int e = 0; e < 12; ++e) cv[J][e] = cp[e];
+      kcs[J] = 16 * ((16 * J + j) / 6 < N - 1 ? (16 * J + j) / 6 : N - 1);
+    }
+    // row 4 iv + g's offset 16 N ((4 iv + g) / 6) in the pair table: the quotient is that of 4 iv,
+    // plus one in DPP rows 2, 3 where 4 iv leaves the remainder 4 (a pad row's pairs multiply zeros)
+    const int bump = g >= 2 ? 16 * N : 0;
+    auto krs = [&](auto IV) __attribute__((always_inline)) {
+      constexpr int iv = decltype(IV)::value, q0 = (4 * iv) / 6, rem = (4 * iv) % 6;
+      constexpr int base = 16 * N * (q0 < N - 1 ? q0 : N - 1);
+      if constexpr (rem == 4 && q0 + 1 <= N - 1) return base + bump;
+      else return base;
+    };
+    // register v of block row I (iv = 4 I + v): row 4 iv + g and its pairs in one batch of reads.
+    // (Reading a row ahead of its use, pinned with sched_barrier, leaves one drain in the builder but
+    // takes 250 AGPRs instead of 216: not kept.)
+    sfor<0, 4 * NB>([&](auto IV) __attribute__((always_inline)) {
+      constexpr int iv = decltype(IV)::value, I = iv / 4, v = iv % 4;
+      if constexpr (4 * iv < NI) {
+        const double* rp = tab + TS * (4 * iv + g);
+        double rv[12];
+        double2 ba[NB];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) rv[e] = rp[e];
+#pragma unroll
+        for (int J = I; J < NB; ++J)
+          ba[J] = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(pt) + (krs(IV) + kcs[J]));
+#pragma unroll
+        for (int J = I; J < NB; ++J) {
+          double av = 0.0, aw = 0.0;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) {
+            av = __builtin_fma(rv[e], cv[J][e], av);
+            aw = __builtin_fma(rv[6 + e], cv[J][6 + e], aw);
+          }
+          const double x = __builtin_fma(ba[J].y, aw, ba[J].x * av);
+          X[I][J][v] = x + ((I == J && j == 4 * v + g) ? 1.0 : 0.0);
+        }
+      } else {  // rows of the pad: the identity
+#pragma unroll
+        for (int J = I; J < NB; ++J) X[I][J][v] = (I == J && j == 4 * v + g) ? 1.0 : 0.0;
+      }
+    });
+  }
+}
+#endif
+
 // ---- factorization (once per rho) ----------------------------------------------------------------
 // Inputs: sc.Rt (R'_k foot blocks, written by the caller's variable lanes), sm.Bw.  Outputs: Q and
 // B in LDS and, per lane, RI[r][3] (row a of R'^-1 of its foot, variable role).
@@ -639,20 +790,42 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
   mark(21);  // R'^-1 per foot done
   // row c of B6 R'^-1: rows 0-2 of B6 are B_w (3 x 12), rows 3-5 dt/m on the matching component
   double br[12];
+  // Branch-free (TILED): a branch on the lane's component c per entry compiles to 24 divergent
+  // blocks, each with its own reads and its own drain of the LDS queue.  The step's four R'^-1 blocks
+  // and the lane's row of B_w are read in one batch instead, both expressions formed, and one selected.
+  if constexpr (SchurCfg<N>::TILED) {
+    double ri[4][9], bw[12];
+    const double* bwp = sm.Bw[k][c < 3 ? c : 0];
 #pragma unroll
-  for (int l = 0; l < 4; ++l)
+    for (int l = 0; l < 4; ++l)
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const double* ri = sc.Ri[k][l];
-      double s;
-      if (c < 3) {
-        const double* bw = sm.Bw[k][c < 3 ? c : 0] + 3 * l;
-        s = (bw[0] * ri[b] + bw[1] * ri[3 + b]) + bw[2] * ri[6 + b];
-      } else {
-        s = dtm * ri[3 * (c - 3) + b];
+      for (int e = 0; e < 9; ++e) ri[l][e] = sc.Ri[k][l][e];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) bw[j] = bwp[j];
+#pragma unroll
+    for (int l = 0; l < 4; ++l)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const double sw = (bw[3 * l] * ri[l][b] + bw[3 * l + 1] * ri[l][3 + b]) + bw[3 * l + 2] * ri[l][6 + b];
+        const double sv = dtm * sel3(c - 3, ri[l][b], ri[l][3 + b], ri[l][6 + b]);
+        br[3 * l + b] = c < 3 ? sw : sv;
       }
-      br[3 * l + b] = s;
-    }
+  } else {
+#pragma unroll
+    for (int l = 0; l < 4; ++l)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const double* ri = sc.Ri[k][l];
+        double s;
+        if (c < 3) {
+          const double* bw = sm.Bw[k][c < 3 ? c : 0] + 3 * l;
+          s = (bw[0] * ri[b] + bw[1] * ri[3 + b]) + bw[2] * ri[6 + b];
+        } else {
+          s = dtm * ri[3 * (c - 3) + b];
+        }
+        br[3 * l + b] = s;
+      }
+  }
   if (iv)
 #pragma unroll
     for (int j = 0; j < 12; ++j) sc.B6R[i][j] = br[j];
@@ -762,40 +935,18 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
     smax = wave_max(iv ? sii : 0.0);
   }
   mark(13);
-  // S - I = L'CL = beta o (V V') + alpha o (W W') (V, W: the 6-column halves of vw; beta, alpha per
-  // step pair), row i in absolute column order, by row_newbcast dot products against four row
-  // copies of each column: no LDS.  Entry (i, m) is the same fma chains by lanes i and m and the
-  // same symmetric coefficients, so S is exactly symmetric.
-  double S[64];
+  // the lane's rows of R'^-1, read back from the scratch (before Q overwrites it)
+  auto read_ri = [&]() __attribute__((always_inline)) {
 #pragma unroll
-  for (int m = 0; m < 64; ++m) S[m] = 0.0;
-  sfor<0, 2>([&](auto PART) __attribute__((always_inline)) {
-    constexpr int part = decltype(PART)::value;
-    double xc[4][6], v6[6];
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-      v6[e] = vw[6 * part + e];
-      rowbcast4(v6[e], xc[0][e], xc[1][e], xc[2][e], xc[3][e]);
+    for (int r = 0; r < R; ++r) {
+      const int kk = 4 * r + ig;
+      const int kc = kk < N ? kk : N - 1;
+      const double* ri = sc.Ri[kc][leg] + 3 * (av ? a : 2);
+      RI[r][0] = ri[0];
+      RI[r][1] = ri[1];
+      RI[r][2] = ri[2];
     }
-    sfor<0, (NI + 3) / 4>([&](auto B) __attribute__((always_inline)) {
-      constexpr int m0 = 4 * decltype(B)::value, sr = m0 >> 4, l0 = m0 & 15;
-      double acc[4] = {0.0, 0.0, 0.0, 0.0};
-      dot6x4<(m0 & 15) == 0, l0, l0 + 1, l0 + 2, l0 + 3>(xc[sr], v6, acc[0], acc[1], acc[2], acc[3]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = m0 + j;
-        if (m < NI) {
-          const int l = m / 6;
-          if constexpr (part == 0) S[m] = (double)(N - (k > l ? k : l)) * acc[j];
-          else S[m] = fma(alpha_jl(N, k, l), acc[j], S[m]);
-        }
-      }
-    });
-  });
-  // S holds L'CL so far: the sweep adds the identity (schur_gj_valu: to each diagonal entry when its
-  // pivot comes, entry (j, j) being read first by pivot j; the MFMA forms: to the tiles) and pad rows
-  // stay 0.
-  mark(14);
+  };
 #if MPCQP_GJ_MFMA
   // internal marks: cycle counts kept in registers, recorded after the sweep (no branch inside it)
   // (the sweep stamps 60 and 61, then 62, 63, 64 per block row, without 63 in the last)
@@ -811,37 +962,41 @@ __device__ __forceinline__ void schur_factor(SM& sm, SchurLds<N>& F, const mpcqp
 #endif
     (void)id;
   };
-  schur_gj_mfma<N>(
-      S, F, t,
-      [&]() __attribute__((always_inline)) {
-        // the lane's rows of R'^-1, read back from the scratch (before Q overwrites it)
+  if constexpr (SchurCfg<N>::TILED) {
+    mf4 X[NB][NB];
+    schur_build_tiles<N>(sc, vw, t, k, X);
+#ifdef MPCQP_PHASE_TIMING
+    // (timing builds only: the tiles pinned here, without which this compiler's register allocation
+    // crashes on the timing build, as it did for a record inside the KKT solve, mpcqp_wave.hip mark 53)
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const int kk = 4 * r + ig;
-          const int kc = kk < N ? kk : N - 1;
-          const double* ri = sc.Ri[kc][leg] + 3 * (av ? a : 2);
-          RI[r][0] = ri[0];
-          RI[r][1] = ri[1];
-          RI[r][2] = ri[2];
+    for (int I = 0; I < NB; ++I)
+#pragma unroll
+      for (int J = I; J < NB; ++J)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          double x = X[I][J][v];
+          keep(x);
+          X[I][J][v] = x;
         }
-      },
-      stamp);
+#endif
+    mark(14);
+    schur_gj_tiles<N>(X, F, t, read_ri, stamp);
+  } else {
+    double S[64];
+    schur_build_rows<N>(vw, k, S);
+    mark(14);
+    schur_gj_mfma<N>(S, F, t, read_ri, stamp);
+  }
   wave_sync();
   mark(15);  // (after the stores to Q: f_gj covers them)
   for (int e = 0; e < ng; ++e) mark(gid[e], gts[e]);
 #else
+  double S[64];
+  schur_build_rows<N>(vw, k, S);
+  mark(14);
   schur_gj_valu<N>(S, F, t, [&]() __attribute__((always_inline)) {
     mark(15);
-    // the lane's rows of R'^-1, read back from the scratch (before Q overwrites it)
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int kk = 4 * r + ig;
-      const int kc = kk < N ? kk : N - 1;
-      const double* ri = sc.Ri[kc][leg] + 3 * (av ? a : 2);
-      RI[r][0] = ri[0];
-      RI[r][1] = ri[1];
-      RI[r][2] = ri[2];
-    }
+    read_ri();
   });
 #endif
 }

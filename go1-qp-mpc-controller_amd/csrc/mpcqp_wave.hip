@@ -511,6 +511,10 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
   for (int iter = 1; iter <= p.max_iter; ++iter) {
     if (need_factor) {
       WV_MARK(10);
+#ifdef MPCQP_FACTOR_REPS  // (measurement builds only: every factorization done this many times)
+#pragma nounroll
+      for (int frep = 0; frep < MPCQP_FACTOR_REPS; ++frep) {
+#endif
       // R'_k foot blocks: c 2r + D^-1 (sigma I + A~' diag(rho) A~) D^-1
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -561,6 +565,9 @@ __device__ __forceinline__ int wave_solve(const int inst, WSmem<N, KS>& sm, cons
         if (t == 0) im[SI::DEGEN] = smax;
       }
       wave_sync();
+#ifdef MPCQP_FACTOR_REPS
+      }
+#endif
       need_factor = false;
       WV_MARK(12);
     }
