@@ -1342,6 +1342,48 @@ int32_t orc_solver_step(orc_solver* s, const double* rec, mpcqp_result* res, dou
   return MPCQP_OK;
 }
 
+/* TEST ONLY — what the persistent solver carries to its next tick (read-only; see mpc_oracle.h). */
+int32_t orc_solver_state(const orc_solver* s, int32_t* initialized, int32_t* last_mode, double* rho, double* c,
+                         double* mu, double* D, double* E, double* q, double* x, double* z, double* y, double* ak0,
+                         double* ak1, uint8_t* pzero) {
+  if (!s || !initialized) return MPCQP_ERR_INVALID_ARG;
+  *initialized = s->initialized;
+  if (!s->initialized) return MPCQP_OK;
+  const osqp_ws* w = &s->w;
+  const int n = w->n, m = w->m;
+  if (last_mode) *last_mode = s->last_mode;
+  if (rho) *rho = w->rho;
+  if (c) *c = w->c;
+  if (mu) *mu = w->mu;
+  if (D) memcpy(D, w->D, sizeof(double) * n);
+  if (E) memcpy(E, w->E, sizeof(double) * m);
+  if (q) memcpy(q, w->q, sizeof(double) * n);
+  if (x) memcpy(x, w->x, sizeof(double) * n);
+  if (z) memcpy(z, w->z, sizeof(double) * m);
+  if (y) memcpy(y, w->y, sizeof(double) * m);
+  if (ak0 && ak1) {
+    /* A~ is block diagonal over the feet (ConvexMpc.cpp:46-58): rows 5f..5f+4 on columns 3f..3f+2 */
+    memset(ak0, 0, sizeof(double) * m);
+    memset(ak1, 0, sizeof(double) * m);
+    for (int j = 0; j < n; ++j)
+      for (int k = w->A.p[j]; k < w->A.p[j + 1]; ++k) {
+        const int i = w->A.i[k];
+        if (i / 5 != j / 3) return MPCQP_ERR_INVALID_ARG;
+        if (j % 3 == 2)
+          ak1[i] = w->A.x[k];
+        else
+          ak0[i] = w->A.x[k];
+      }
+  }
+  if (pzero) {
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) pzero[(size_t)i * n + j] = i <= j;
+    for (int j = 0; j < n; ++j)
+      for (int k = w->P.p[j]; k < w->P.p[j + 1]; ++k) pzero[(size_t)w->P.i[k] * n + j] = 0;
+  }
+  return MPCQP_OK;
+}
+
 /* T ticks of `batch` independent robots: recs [T][batch][rec], res [T][batch]. */
 typedef struct {
   const mpcqp_params* prm;

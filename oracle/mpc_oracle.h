@@ -79,6 +79,18 @@ int32_t orc_solve_sequence(const mpcqp_params* prm, const double* recs, int32_t 
 int32_t orc_scale_image(const mpcqp_params* prm, const double* rec, double* D, double* E, double* q, double* c);
 int32_t orc_solver_step_image(orc_solver* s, const double* rec, mpcqp_result* res, double* D, double* E, double* q,
                               double* c, int32_t* mode);
+/* TEST ONLY: what a persistent solver carries from the step it just ran to its next one.  Read-only: a
+ * step, a step on a non-finite record (state untouched) and a reset (uninitialized) behave as without
+ * it.  *initialized is always written; the rest only for an initialized solver (any pointer but
+ * `initialized` may be NULL): last_mode (the last step's branch, as orc_solver_step_image), the adapted
+ * rho, the cost scaling c, the mu the constraint matrix was built with, the scaling D [12N] and E [20N],
+ * the scaled gradient q~ [12N], the scaled iterates x [12N], z [20N], y [20N], the non-zeros of the
+ * scaled constraint matrix A~ per row ([20N] each: ak0 the entry on the foot's fx or fy column, 0 on a
+ * foot's fifth row; ak1 the entry on its fz column) and pzero [12N][12N] row-major: 1 where i <= j and
+ * P's upper triangle stores no entry (i, j) (OsqpEigen's sparseView dropped an exact zero), else 0. */
+int32_t orc_solver_state(const orc_solver* s, int32_t* initialized, int32_t* last_mode, double* rho, double* c,
+                         double* mu, double* D, double* E, double* q, double* x, double* z, double* y, double* ak0,
+                         double* ak1, uint8_t* pzero);
 void orc_joint_torques(const double* tq, const double* f_grf, int32_t* counter, double* tau);
 
 /* Batch over `nthreads` POSIX threads (static contiguous partition).  sols may be NULL. */

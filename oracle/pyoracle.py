@@ -153,6 +153,9 @@ def lib():
         L.orc_solver_step_image.argtypes = [ctypes.c_void_p, dp, ctypes.c_void_p, dp, dp, dp, dp,
                                             ctypes.POINTER(ctypes.c_int32)]
         L.orc_solver_step_image.restype = ctypes.c_int32
+        ip = ctypes.POINTER(ctypes.c_int32)
+        L.orc_solver_state.argtypes = [ctypes.c_void_p, ip, ip] + [dp] * 11 +[ctypes.POINTER(ctypes.c_uint8)]
+        L.orc_solver_state.restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -256,6 +259,30 @@ class WarmSolver:
         assert rc == 0
         img["c"], img["mode"] = c.value, mode.value
         return np.frombuffer(bytearray(res), dtype=RESULT_DTYPE)[0], img
+
+    def state(self):
+        """TEST ONLY (orc_solver_state, read-only): what the solver carries to its next tick.
+        {initialized}, and for an initialized solver also {last_mode, rho, c, mu, D [12N], E [20N],
+        q (= c D q) [12N], scaled x [12N], z [20N], y [20N], ak0 / ak1 [20N] (A~'s entry of each row on the
+        foot's fx or fy column / on its fz column), pzero [12N][12N] bool (upper-triangle entries of P that
+        the sparse matrix does not store)}."""
+        N = self.params.horizon
+        n, m = 12 * N, 20 * N
+        st = {k: np.zeros(n) for k in ("D", "q", "x")}
+        st.update({k: np.zeros(m) for k in ("E", "z", "y", "ak0", "ak1")})
+        pz = np.zeros((n, n), dtype=np.uint8)
+        init, mode = ctypes.c_int32(), ctypes.c_int32()
+        sc = [ctypes.c_double() for _ in range(3)]
+        rc = lib().orc_solver_state(self._s, ctypes.byref(init), ctypes.byref(mode),
+                                    *[ctypes.cast(ctypes.byref(v), ctypes.POINTER(ctypes.c_double)) for v in sc],
+                                    *[_dp(st[k]) for k in ("D", "E", "q", "x", "z", "y", "ak0", "ak1")],
+                                    pz.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+        assert rc == 0
+        if not init.value:
+            return {"initialized": False}
+        st.update(initialized=True, last_mode=mode.value, rho=sc[0].value, c=sc[1].value, mu=sc[2].value,
+                  pzero=pz.astype(bool))
+        return st
 
     def reset(self):
         lib().orc_solver_reset(self._s)

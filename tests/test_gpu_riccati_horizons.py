@@ -145,7 +145,8 @@ def test_trace_close_to_oracle(oracle, N):
 @pytest.mark.parametrize("N", [6, 11, 13, 18])
 def test_warm_ticks(oracle, N):
     """Three warm-started ticks with a change of the contact pattern inside, per tick against the oracle's
-    persistent solvers."""
+    persistent solvers.  (Contacts enter the bounds only: every tick after the first is an osqp_update_P tick.
+    tests/test_gpu_warm_slot.py has the re-init ticks.)"""
     T = 3
     ticks = mpcqp.records.synthetic_go1_ticks(B, T, seed=5200 + N, gait="trot", swing_ticks=3)
     recs_t = np.stack([mpcqp.assemble_compute_grf(s, N) for s in ticks])

@@ -16,8 +16,9 @@ Schur parity tests (test_gpu_lds_flight, test_gpu_degenerate), the screen's hand
 the host restatement's prediction (degenerate_cases.gram_ratio).  The seeds were chosen on the CPU so
 that the oracle alone refactorizes: at least a quarter of every batch has rho_updates >= 2 in the
 oracle's results (0.33 .. 0.95 with these seeds), which is asserted on the oracle's output.  Plus a
-batch of one robot, and a warm sequence of three ticks across a contact change at N = 10 (the
-update_P and re-init branches refactorize with an inherited rho)."""
+batch of one robot, and a warm sequence of three ticks across a contact change at N = 10 (contacts
+enter the bounds only, so both later ticks take the update_P branch, which refactorizes with an
+inherited rho and, where a row's kind changed, a new rho vector)."""
 import numpy as np
 import pytest
 import torch
@@ -79,7 +80,8 @@ def test_a_batch_of_one(oracle, N):
 
 def test_warm_ticks_across_a_contact_change(oracle):
     """Trot with the stance pair switched every second tick and a per-robot phase: between ticks 0, 1
-    and 2 every robot changes its contacts once (re-init) and keeps them once (update_P)."""
+    and 2 every robot changes its contacts once (the bounds and the rho vector of the rows whose kind
+    changed) and keeps them once; both are update_P ticks, as H's zero pattern and mu stay."""
     T, N = 3, 10
     ticks = mpcqp.records.synthetic_go1_ticks(B, T, seed=5210, gait="trot", swing_ticks=2)
     change = np.stack([np.any(ticks[t].contacts != ticks[t - 1].contacts, axis=1) for t in range(1, T)])

@@ -68,12 +68,34 @@ def test_warm_sequence_matches_oracle(oracle, gait):
 
 
 def test_warm_pattern_change_reinit(oracle):
-    """test_mpc's stance has exact zeros in H (upper triangle); a rotated copy is dense.  Going
-    sparse -> dense -> dense -> sparse takes OsqpEigen's re-init branch, update_P, re-init."""
+    """test_mpc's stance has exact zeros in H (upper triangle).  A yaw rotation (feet rotated along) keeps that zero
+    pattern: level -> yaw -> yaw -> level is setup and then osqp_update_P on every tick, branches [0, 1, 1, 1] on the
+    oracle.  A pitched or rolled copy is dense: level -> pitch -> roll -> level takes OsqpEigen's re-init, update_P
+    and the re-init again, branches [0, 2, 1, 2].  (tests/test_gpu_warm_slot.py looks at the branch and the slot of
+    every such tick on the device; here the results.)"""
     rec, q, r = mpcqp.assemble_test_mpc(10)
     p = mpcqp.default_params(10, q_weights=q, r_weights=r)
-    P0, *_ = oracle.build_qp(oracle.default_params(10, q=list(q), r=list(r)), rec)
+    op = oracle.default_params(10, q=list(q), r=list(r))
+    P0, *_ = oracle.build_qp(op, rec)
     assert np.sum(np.triu(P0) == 0) > 120 * 119 // 2  # exact zeros above the diagonal
+
+    def modes(seq):
+        w = oracle.WarmSolver(op)
+        out = [w.step_image(x[0])[1]["mode"] for x in seq]
+        w.close()
+        return out
+
+    def posed(roll, pitch):
+        x = rec.copy()
+        x[mpcqp._lib.REC_EULER:mpcqp._lib.REC_EULER + 2] = (roll, pitch)
+        x[mpcqp._lib.REC_X0:mpcqp._lib.REC_X0 + 2] = (roll, pitch)
+        x[mpcqp._lib.REC_ROT:mpcqp._lib.REC_ROT + 9] = mpcqp.records.rot_zyx(
+            np.array([roll]), np.array([pitch]), np.array([0.0]))[0].reshape(9)
+        return x
+    tilt = np.stack([rec, posed(0.0, 0.2), posed(0.2, 0.0), rec])[:, None, :]
+    assert modes(tilt) == [0, 2, 1, 2]
+    _check(_gpu_sequence(p, tilt), _oracle_sequence(oracle, p, tilt), "pattern change (pitch, roll)", min_iter_equal=1.0)
+
     def rotated(yaw):
         x = rec.copy()
         c, s_ = np.cos(yaw), np.sin(yaw)
@@ -86,6 +108,7 @@ def test_warm_pattern_change_reinit(oracle):
         x[f:f + 120] = np.einsum("ij,klj->kli", Rz, feet).reshape(120)
         return x
     seq = np.stack([rec, rotated(0.3), rotated(0.31), rec])[:, None, :]
+    assert modes(seq) == [0, 1, 1, 1]
     got = _gpu_sequence(p, seq)
     ref = _oracle_sequence(oracle, p, seq)
     _check(got, ref, "pattern change", min_iter_equal=1.0)
