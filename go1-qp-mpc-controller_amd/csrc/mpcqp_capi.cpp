@@ -906,6 +906,23 @@ int32_t mpcqp_plant_step_wrench_device(const mpcqp_plant_params* pp, double dt, 
              : MPCQP_ERR_HIP;
 }
 
+int32_t mpcqp_plant_step_terrain_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                        const double* d_wrench, const double* d_terrain, int32_t terrain_rows,
+                                        const double* d_episode_state, int32_t batch, double* d_plant_state,
+                                        const double* d_plant_init, double* d_sensors, double* d_plan_in,
+                                        double* d_states, double* d_tq_records, double* d_plant_out, void* stream) {
+  if (!pp || batch < 0 || !(dt > 0.0) || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
+  if (pp->substeps < 1 || pp->substeps > 16) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_joint_torques || !d_plant_state)) return MPCQP_ERR_INVALID_ARG;
+  if (d_terrain && (terrain_rows < 1 || (!d_episode_state && terrain_rows < batch))) return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_plant_terrain(*pp, dt, d_joint_torques, d_wrench, d_terrain, terrain_rows, d_episode_state,
+                                     batch, d_plant_state, d_plant_init, d_sensors, d_plan_in, d_states, d_tq_records,
+                                     d_plant_out, stream) == hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
 void mpcqp_disturb_default_params(mpcqp_disturb_params* p) {
   if (!p) return;
   p->load_mass_max = 0.0;

@@ -139,6 +139,12 @@ hipError_t launch_plant(const mpcqp_plant_params& pp, double dt, const double* t
 hipError_t launch_plant_wrench(const mpcqp_plant_params& pp, double dt, const double* torques, const double* wrench,
                                int batch, double* slots, const double* init, double* sensors, double* plan_in,
                                double* states, double* tq, double* out, void* stream);
+// the same on the inclined ground of a terrain table (terrain != nullptr), two more instantiations; robot b's row
+// is its episode slot's pool index, or b without an episode slot
+hipError_t launch_plant_terrain(const mpcqp_plant_params& pp, double dt, const double* torques, const double* wrench,
+                                const double* terrain, int terrain_rows, const double* episode_state, int batch,
+                                double* slots, const double* init, double* sensors, double* plan_in, double* states,
+                                double* tq, double* out, void* stream);
 
 // Disturbance stage: pushes, payload weight, sensor noise and IMU biases drawn on the device (mpcqp_disturb.hip)
 hipError_t launch_disturb(const mpcqp_disturb_params& dp, const mpcqp_disturb_buffers& bf, int batch, void* stream);

@@ -6,10 +6,11 @@
 // feet turn the joint torques into ground reactions f = -R J^-T tau (the inverse of mpcqp_torque.hip's
 // tau = J^T (-f_grf)), joint-space swing legs that exert nothing on the trunk, flat ground z = 0,
 // semi-implicit Euler in `substeps` substeps per tick; optionally two external forces on the trunk (the wrench
-// row of mpcqp_plant_step_wrench_device).  A held foot does not slip.  Left out: leg mass,
-// the swing legs' reaction on the trunk, foot slip, terrain, joint limits, and impact dynamics beyond
-// zeroing the landing foot's velocity.  The joint inertias are the model's own choice, not identified
-// from a robot description.
+// row of mpcqp_plant_step_wrench_device), and optionally a per-robot inclined ground with its own friction
+// coefficient (the terrain row of mpcqp_plant_step_terrain_device).  A held foot does not slip.  Left out: leg
+// mass, the swing legs' reaction on the trunk, foot slip, height fields and steps, trunk-ground contact, joint
+// limits, and impact dynamics beyond zeroing the landing foot's velocity.  The joint inertias are the model's
+// own choice, not identified from a robot description.
 //
 // One thread per (robot, leg); the four legs of a robot are the four lanes of one DPP quad, 16 robots
 // per wave (as mpcqp_torque.hip and mpcqp_legplan.hip).  The trunk state is held, and its update is
@@ -174,15 +175,33 @@ __device__ __forceinline__ bool kinematics(const Leg& g, State& s, double (&R)[9
   return ok;
 }
 
+// The ground of a terrain row: {p : n.p = d}, friction mu.  hgt and dot in the grouping of the statement.
+struct Ground {
+  double n[3], d, mu;
+};
+__device__ __forceinline__ double dot(const Ground& t, const double (&v)[3]) {
+#pragma clang fp contract(off)
+  return (t.n[0] * v[0] + t.n[1] * v[1]) + t.n[2] * v[2];
+}
+__device__ __forceinline__ double hgt(const Ground& t, const double (&p)[3]) {
+#pragma clang fp contract(off)
+  return dot(t, p) - t.d;
+}
+
 // WRENCH: the external forces of a wrench row act on the trunk (include/mpcqp.h has the statement).  Without it
 // the row is never read, and the instantiation is the kernel as it was before the wrench existed.
-template <bool WRENCH>
+// TERRAIN: the ground is the inclined plane of the robot's terrain row, with the row's friction coefficient: the
+// four places marked "terrain" below (include/mpcqp.h has the statement).  Without it neither the table nor the
+// episode slot is read, and the instantiation is the kernel as it was before the terrain existed.
+template <bool WRENCH, bool TERRAIN>
 __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp, const double dt,
                                                     const double* __restrict__ torques, const int batch,
                                                     double* __restrict__ slots, const double* __restrict__ init,
                                                     double* __restrict__ sensors, double* __restrict__ plan_in,
                                                     double* __restrict__ states, double* __restrict__ tq,
-                                                    double* __restrict__ out, const double* __restrict__ wrench) {
+                                                    double* __restrict__ out, const double* __restrict__ wrench,
+                                                    const double* __restrict__ terrain, const int terrain_rows,
+                                                    const double* __restrict__ episode_state) {
 #pragma clang fp contract(off)
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = gid >> 2, leg = gid & 3;
@@ -208,6 +227,24 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
       P1[k] = wr[MPCQP_PW_POINT1 + k];
       finite = finite && __builtin_isfinite(F0[k]) && __builtin_isfinite(P0[k]) && __builtin_isfinite(F1[k]) &&
                __builtin_isfinite(P1[k]);
+    }
+  }
+  // the terrain row, alike on the four lanes and read once per tick: the robot's own, or with an episode slot
+  // the one of its pool index.  An index outside the table is a non-finite row, and nothing is read there.
+  Ground gr = {{0.0, 0.0, 1.0}, 0.0, pp.mu};
+  if constexpr (TERRAIN) {
+    double idx = (double)b;
+    if (episode_state) idx = episode_state[(size_t)MPCQP_ES_SIZE * b + MPCQP_ES_POOL];
+    const bool inside = idx > -1.0 && idx < (double)terrain_rows;  // (int) truncates towards zero; a NaN is outside
+    finite = finite && inside;
+    if (inside) {
+      const double* tr = terrain + (size_t)MPCQP_TR_SIZE * (int)idx;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) gr.n[k] = tr[MPCQP_TR_NORMAL + k];
+      gr.d = tr[MPCQP_TR_OFFSET];
+      gr.mu = tr[MPCQP_TR_MU];
+      finite = finite && __builtin_isfinite(gr.n[0]) && __builtin_isfinite(gr.n[1]) && __builtin_isfinite(gr.n[2]) &&
+               __builtin_isfinite(gr.d) && __builtin_isfinite(gr.mu);
     }
   }
   if (quad_any(!finite)) {
@@ -269,8 +306,17 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
     }
     s.st = false;
     kinematics(g, s, R, p_b, J);  // as a swing leg: the foot from the joints
-    s.st = s.foot[2] <= 0.0;
-    if (s.st) s.foot[2] = 0.0;
+    if constexpr (TERRAIN) {  // terrain 1: held iff on or under the plane, and put on it
+      const double hf = hgt(gr, s.foot);
+      s.st = hf <= 0.0;
+      if (s.st) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s.foot[k] = s.foot[k] - hf * gr.n[k];
+      }
+    } else {
+      s.st = s.foot[2] <= 0.0;
+      if (s.st) s.foot[2] = 0.0;
+    }
   } else {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -304,16 +350,32 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
         }
         lu3_solve(At, bt, gl);
         mat_vec(R, gl, fw);
-        const double fz = -fw[2];
-        if (fz < 0.0) {
-          s.st = false;
+        if constexpr (TERRAIN) {  // terrain 2: the normal part decides, the tangential part is scaled onto the cone
+          const double fg[3] = {-fw[0], -fw[1], -fw[2]};
+          const double fn = dot(gr, fg);
+          if (fn < 0.0) {
+            s.st = false;
+          } else {
+            double t[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) t[k] = fg[k] - fn * gr.n[k];
+            const double ft = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]), lim = gr.mu * fn;
+            const double sc = ft > lim ? lim / ft : 1.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) f[k] = fn * gr.n[k] + sc * t[k];
+          }
         } else {
-          const double fx = -fw[0], fy = -fw[1];
-          const double ft = sqrt(fx * fx + fy * fy), lim = pp.mu * fz;
-          const double sc = ft > lim ? lim / ft : 1.0;
-          f[0] = fx * sc;
-          f[1] = fy * sc;
-          f[2] = fz;
+          const double fz = -fw[2];
+          if (fz < 0.0) {
+            s.st = false;
+          } else {
+            const double fx = -fw[0], fy = -fw[1];
+            const double ft = sqrt(fx * fx + fy * fy), lim = pp.mu * fz;
+            const double sc = ft > lim ? lim / ft : 1.0;
+            f[0] = fx * sc;
+            f[1] = fy * sc;
+            f[2] = fz;
+          }
         }
       }
       if (!s.st) {
@@ -403,10 +465,23 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
         mat_vec(J2, s.qd, jq);
 #pragma unroll
         for (int k = 0; k < 3; ++k) u[k] = wp[k] + jq[k];
-        const double fvz = s.v[2] + ((R2[6] * u[0] + R2[7] * u[1]) + R2[8] * u[2]);
-        if (s.foot[2] <= 0.0 && fvz < 0.0) {
-          s.foot[2] = 0.0;
-          s.st = true;
+        if constexpr (TERRAIN) {  // terrain 3: lands on or under the plane while moving into it
+          double ru[3], fv[3];
+          mat_vec(R2, u, ru);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) fv[k] = s.v[k] + ru[k];
+          const double hf = hgt(gr, s.foot);
+          if (hf <= 0.0 && dot(gr, fv) < 0.0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s.foot[k] = s.foot[k] - hf * gr.n[k];
+            s.st = true;
+          }
+        } else {
+          const double fvz = s.v[2] + ((R2[6] * u[0] + R2[7] * u[1]) + R2[8] * u[2]);
+          if (s.foot[2] <= 0.0 && fvz < 0.0) {
+            s.foot[2] = 0.0;
+            s.st = true;
+          }
         }
       }
     }
@@ -422,7 +497,12 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
     }
     return;
   }
-  const double status = s.pos[2] < pp.min_height ? 2.0 : 0.0;
+  double status;
+  if constexpr (TERRAIN) {  // terrain 4: the trunk's height over the plane
+    status = hgt(gr, s.pos) < pp.min_height ? 2.0 : 0.0;
+  } else {
+    status = s.pos[2] < pp.min_height ? 2.0 : 0.0;
+  }
 
   // ---- stores: each lane its leg, leg 0 the trunk ----
 #pragma unroll
@@ -551,8 +631,9 @@ hipError_t launch_plant(const mpcqp_plant_params& pp, double dt, const double* t
                         const double* init, double* sensors, double* plan_in, double* states, double* tq,
                         double* out, void* stream) {
   const int threads = 4 * batch;
-  hipLaunchKernelGGL(plant::plant_kernel<false>, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, pp,
-                     dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, (const double*)nullptr);
+  hipLaunchKernelGGL((plant::plant_kernel<false, false>), dim3((threads + 255) / 256), dim3(256), 0,
+                     (hipStream_t)stream, pp, dt, torques, batch, slots, init, sensors, plan_in, states, tq, out,
+                     (const double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr);
   return hipGetLastError();
 }
 
@@ -561,8 +642,27 @@ hipError_t launch_plant_wrench(const mpcqp_plant_params& pp, double dt, const do
                                double* states, double* tq, double* out, void* stream) {
   if (!wrench) return launch_plant(pp, dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, stream);
   const int threads = 4 * batch;
-  hipLaunchKernelGGL(plant::plant_kernel<true>, dim3((threads + 255) / 256), dim3(256), 0, (hipStream_t)stream, pp,
-                     dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, wrench);
+  hipLaunchKernelGGL((plant::plant_kernel<true, false>), dim3((threads + 255) / 256), dim3(256), 0,
+                     (hipStream_t)stream, pp, dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, wrench,
+                     (const double*)nullptr, 0, (const double*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_plant_terrain(const mpcqp_plant_params& pp, double dt, const double* torques, const double* wrench,
+                                const double* terrain, int terrain_rows, const double* episode_state, int batch,
+                                double* slots, const double* init, double* sensors, double* plan_in, double* states,
+                                double* tq, double* out, void* stream) {
+  if (!terrain)
+    return launch_plant_wrench(pp, dt, torques, wrench, batch, slots, init, sensors, plan_in, states, tq, out, stream);
+  const int threads = 4 * batch;
+  const dim3 grid((threads + 255) / 256), block(256);
+  if (wrench)
+    hipLaunchKernelGGL((plant::plant_kernel<true, true>), grid, block, 0, (hipStream_t)stream, pp, dt, torques, batch,
+                       slots, init, sensors, plan_in, states, tq, out, wrench, terrain, terrain_rows, episode_state);
+  else
+    hipLaunchKernelGGL((plant::plant_kernel<false, true>), grid, block, 0, (hipStream_t)stream, pp, dt, torques, batch,
+                       slots, init, sensors, plan_in, states, tq, out, (const double*)nullptr, terrain, terrain_rows,
+                       episode_state);
   return hipGetLastError();
 }
 

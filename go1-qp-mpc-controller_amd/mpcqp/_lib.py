@@ -54,6 +54,8 @@ PN_FOOT, PN_CONTACT, PN_ACC, PN_STATUS, PN_SIZE = 38, 50, 54, 57, 64
 PI_POS, PI_QUAT, PI_JOINT_POS, PI_SIZE = 0, 3, 7, 20
 PT_POS, PT_QUAT, PT_EULER, PT_LIN_VEL, PT_ANG_VEL, PT_CONTACTS, PT_GRF, PT_FOOT, PT_ACC = 0, 3, 7, 10, 13, 16, 20, 32, 44
 PT_STATUS, PT_SIZE = 47, 48
+# terrain row of the plant stage (include/mpcqp.h MPCQP_TR_*)
+TR_NORMAL, TR_OFFSET, TR_MU, TR_SIZE = 0, 3, 4, 8
 
 
 def rec_feet(N):
@@ -244,6 +246,7 @@ EXPORTED = [
     "mpcqp_episode_state_size", "mpcqp_episode_device",
     "mpcqp_plant_step_wrench_device", "mpcqp_disturb_default_params", "mpcqp_disturb_params_size",
     "mpcqp_disturb_buffers_size", "mpcqp_disturb_device",
+    "mpcqp_plant_step_terrain_device",
 ]
 
 _libs = {}
@@ -421,6 +424,10 @@ def load(debug=False):
             raise MpcQpError(f"ABI mismatch: mpcqp_disturb_params / _buffers are {L.mpcqp_disturb_params_size()} / "
                              f"{L.mpcqp_disturb_buffers_size()} bytes in C, {ctypes.sizeof(DisturbParams)} / "
                              f"{ctypes.sizeof(DisturbBuffers)} in ctypes")
+    if hasattr(L, "mpcqp_plant_step_terrain_device"):  # (absent from an older library given by MPCQP_LIB for an A/B)
+        L.mpcqp_plant_step_terrain_device.argtypes = [ctypes.POINTER(PlantParams), ctypes.c_double, vp, vp, vp, i32, vp,
+                                                      i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mpcqp_plant_step_terrain_device.restype = i32
     if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
         raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
                          f"{ctypes.sizeof(EstimatorParams)} in ctypes")

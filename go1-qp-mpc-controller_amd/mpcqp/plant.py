@@ -3,9 +3,10 @@
 Per robot and per tick the device stage advances a rigid-body model of the robot by one control period
 under the tick's joint torques and writes the next tick's sensor-level rows: a single rigid trunk on
 massless stance legs (a held foot turns the joint torques into the ground reaction f = -R J^-T tau),
-joint-space swing legs, flat ground, semi-implicit Euler in ``substeps`` substeps.  Left out: leg mass, the
-swing legs' reaction on the trunk, foot slip, terrain, joint limits, and impact dynamics beyond zeroing the
-landing foot's velocity.  The state lives in a per-robot device slot of ``plant_state_size()`` doubles;
+joint-space swing legs, flat ground or (plant_step_terrain_device) a per-robot inclined plane with its own friction
+coefficient, semi-implicit Euler in ``substeps`` substeps.  Left out: leg mass, the swing legs' reaction on the
+trunk, foot slip, height fields and steps, trunk-ground contact, joint limits, and impact dynamics beyond zeroing
+the landing foot's velocity.  The state lives in a per-robot device slot of ``plant_state_size()`` doubles;
 zero-filled = fresh, and zeroing a robot's slots is how a fleet resets a fallen robot (a robot whose status
 is not 0 is frozen until then).  The episode stage (episode.py) does that on the device: it ends a fallen
 robot's episode, zeroes its slots over two ticks and restarts it from a drawn start row.
@@ -15,7 +16,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import PI_JOINT_POS, PI_POS, PI_QUAT, PI_SIZE, PlantParams, check, load, override
+from ._lib import (PI_JOINT_POS, PI_POS, PI_QUAT, PI_SIZE, TR_MU, TR_NORMAL, TR_OFFSET, TR_SIZE, PlantParams, check, load,
+                   override)
 
 # the slot (include/mpcqp.h MPCQP_PN_*) and the output row (MPCQP_PT_*)
 PLANT_STATE_DTYPE = np.dtype([
@@ -55,6 +57,126 @@ def pack_plant_init(pos, quat, joint_pos):
     row[:, PI_QUAT:PI_QUAT + 4] = np.asarray(quat, dtype=np.float64).reshape(B, 4)
     row[:, PI_JOINT_POS:PI_JOINT_POS + 12] = np.asarray(joint_pos, dtype=np.float64).reshape(B, 12)
     return row
+
+
+def pack_terrain(normal, offset, mu):
+    """Terrain rows [P, TR_SIZE] (include/mpcqp.h MPCQP_TR_*) of the planes {p : n.p = offset} with friction
+    ``mu``: ``normal`` [P,3] is normalised here; ``offset`` and ``mu`` broadcast over the rows.  Raises on a
+    normal whose z is not positive, a non-finite entry or a negative mu."""
+    n = np.asarray(normal, dtype=np.float64).reshape(-1, 3)
+    P = n.shape[0]
+    d = np.broadcast_to(np.asarray(offset, dtype=np.float64), (P,))
+    m = np.broadcast_to(np.asarray(mu, dtype=np.float64), (P,))
+    if not (np.all(np.isfinite(n)) and np.all(np.isfinite(d)) and np.all(np.isfinite(m))):
+        raise ValueError("pack_terrain: non-finite entry")
+    if np.any(n[:, 2] <= 0.0):
+        raise ValueError("pack_terrain: the normal's z must be positive")
+    if np.any(m < 0.0):
+        raise ValueError("pack_terrain: mu must not be negative")
+    row = np.zeros((P, TR_SIZE))
+    row[:, TR_NORMAL:TR_NORMAL + 3] = n / np.linalg.norm(n, axis=1, keepdims=True)
+    row[:, TR_OFFSET] = d
+    row[:, TR_MU] = m
+    return row
+
+
+def terrain_from_slope(pitch, roll, mu, point=(0.0, 0.0, 0.0)):
+    """Terrain rows of the planes through ``point`` with the normal n = R_y(pitch) R_x(roll) e_z (a robot that
+    heads along +x on a ground of positive pitch looks downhill, as a positive body pitch is nose down); the
+    arguments broadcast over the rows."""
+    pitch, roll, mu = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64).reshape(-1) for a in (pitch, roll, mu)))
+    n = np.stack([np.sin(pitch) * np.cos(roll), -np.sin(roll), np.cos(pitch) * np.cos(roll)], 1)
+    pt = np.broadcast_to(np.asarray(point, dtype=np.float64), n.shape)
+    n = n / np.linalg.norm(n, axis=1, keepdims=True)
+    return pack_terrain(n, np.sum(n * pt, 1), mu)
+
+
+def terrain_height(terrain_rows, p):
+    """hgt(p) = ((n0 p0 + n1 p1) + n2 p2) - d of points p [P, ..., 3] over the planes of the rows [P, TR_SIZE]."""
+    t = np.asarray(terrain_rows, dtype=np.float64).reshape(-1, TR_SIZE)
+    p = np.asarray(p, dtype=np.float64)
+    n = t[:, TR_NORMAL:TR_NORMAL + 3].reshape((t.shape[0],) + (1,) * (p.ndim - 2) + (3,))
+    d = t[:, TR_OFFSET].reshape((t.shape[0],) + (1,) * (p.ndim - 2))
+    return ((n[..., 0] * p[..., 0] + n[..., 1] * p[..., 1]) + n[..., 2] * p[..., 2]) - d
+
+
+def _quat_mul(a, b):
+    aw, ax, ay, az = (a[:, k] for k in range(4))
+    bw, bx, by, bz = (b[:, k] for k in range(4))
+    return np.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], 1)
+
+
+def _quat_rot(q):
+    w, x, y, z = (q[:, k] for k in range(4))
+    return np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                     2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
+
+
+def place_on_terrain(init_rows, terrain_rows, pp=None, point=None, lower=True):
+    """Flat-ground init rows [B, PI_SIZE] (feet on z = 0) placed on the planes of ``terrain_rows`` [B, TR_SIZE]:
+    position and attitude are rotated about the origin by the ground rotation G = R_y(pitch) R_x(roll) with
+    G e_z = n and shifted by ``point`` [B,3] on the plane (default: d n, the plane's point nearest the origin);
+    the trunk is then lowered along n by the highest foot's height over the plane plus 5e-16, so every foot starts
+    held (a foot a few 1e-17 above the ground would start in swing) and none deeper than 1e-15: the feet of a stance
+    differ by a few 1e-17 after the rotation and the lowered position rounds to its last place, which 1e-15 itself
+    would leave no room for.  ``lower=False`` leaves that out, and every foot keeps the height it had over z = 0.
+    ``pp``: the PlantParams whose leg geometry places the feet (default: the library's).  Returns the init rows and
+    the slope-parallel (roll, pitch, yaw) [B,3] of the placed attitude, for root_euler_d."""
+    init = np.array(init_rows, dtype=np.float64).reshape(-1, PI_SIZE)
+    B = init.shape[0]
+    t = np.asarray(terrain_rows, dtype=np.float64).reshape(B, TR_SIZE)
+    n, d = t[:, TR_NORMAL:TR_NORMAL + 3], t[:, TR_OFFSET]
+    pitch, roll = np.arctan2(n[:, 0], n[:, 2]), -np.arcsin(np.clip(n[:, 1], -1.0, 1.0))
+    zero = np.zeros(B)
+    qg = _quat_mul(np.stack([np.cos(pitch / 2), zero, np.sin(pitch / 2), zero], 1),
+                   np.stack([np.cos(roll / 2), np.sin(roll / 2), zero, zero], 1))
+    G = _quat_rot(qg)
+    shift = n * d[:, None] if point is None else np.broadcast_to(np.asarray(point, dtype=np.float64), (B, 3))
+    quat = _quat_mul(qg, init[:, PI_QUAT:PI_QUAT + 4])
+    quat = quat / np.linalg.norm(quat, axis=1, keepdims=True)
+    pos = np.einsum("bij,bj->bi", G, init[:, PI_POS:PI_POS + 3]) + shift
+    pp = default_plant_params() if pp is None else pp
+    feet = _feet_body(pp, init[:, PI_JOINT_POS:PI_JOINT_POS + 12].reshape(B, 4, 3))
+    R = _quat_rot(quat)
+    for again in range(4 if lower else 0):  # (again only for a robot whose highest foot rounded to above the plane)
+        top = terrain_height(t, pos[:, None] + np.einsum("bij,blj->bli", R, feet)).max(1)
+        if again and np.all(top <= 0.0):
+            break
+        pos = pos - np.where((top > 0.0) | (again == 0), top + 5e-16, 0.0)[:, None] * n
+    out = init.copy()
+    out[:, PI_POS:PI_POS + 3] = pos
+    out[:, PI_QUAT:PI_QUAT + 4] = quat
+    euler = np.stack([np.arctan2(R[:, 2, 1], R[:, 2, 2]), np.arcsin(np.clip(-R[:, 2, 0], -1.0, 1.0)),
+                      np.arctan2(R[:, 1, 0], R[:, 0, 0])], 1)
+    return out, euler
+
+
+def _feet_body(pp, q):
+    """Foot positions in the body frame [B,4,3] from joint angles [B,4,3]: the forward kinematics of the plant
+    (csrc/mpcqp_plant.hip fk_jac) on the geometry of ``pp``."""
+    fix = np.array(list(pp.rho_fix), dtype=np.float64).reshape(1, 4, 5)
+    opt = np.array(list(pp.rho_opt), dtype=np.float64).reshape(1, 4, 3)
+    ox, oy, dd, lt, le, a0 = fix[..., 0], fix[..., 1], fix[..., 2] + opt[..., 1], fix[..., 3], fix[..., 4] - opt[..., 2], opt[..., 0]
+    s0, c0, s1, c1 = np.sin(q[..., 0]), np.cos(q[..., 0]), np.sin(q[..., 1]), np.cos(q[..., 1])
+    s12, c12 = np.sin(q[..., 1] + q[..., 2]), np.cos(q[..., 1] + q[..., 2])
+    hh = lt * c1 + (le * c12 + a0 * s12)
+    xx = (a0 * c12 - le * s12) - lt * s1
+    return np.stack([ox + xx, oy + (dd * c0 + hh * s0), dd * s0 - hh * c0], -1)
+
+
+def plant_step_terrain_device(pp, dt, d_torques, d_wrench, d_terrain, terrain_rows, d_episode_state, batch,
+                              d_plant_state, d_init=0, d_sensors=0, d_plan_in=0, d_states=0, d_tq_records=0,
+                              d_plant_out=0, stream=0):
+    """mpcqp_plant_step_terrain_device on device pointers (ints; 0 for the optional ones, d_wrench, d_terrain and
+    d_episode_state among them).  Robot b stands on row (int) episode_state[b][ES_POOL] of the terrain table, or on
+    row b without an episode slot."""
+    check(load().mpcqp_plant_step_terrain_device(
+        ctypes.byref(pp), float(dt), d_torques or None, d_wrench or None, d_terrain or None, int(terrain_rows),
+        d_episode_state or None, int(batch), d_plant_state or None, d_init or None, d_sensors or None,
+        d_plan_in or None, d_states or None, d_tq_records or None, d_plant_out or None, stream or None),
+          None, "mpcqp_plant_step_terrain_device")
 
 
 def plant_step_device(pp, dt, d_torques, batch, d_plant_state, d_init=0, d_sensors=0, d_plan_in=0, d_states=0,

@@ -656,10 +656,12 @@ int32_t mpcqp_policy_device(const mpcqp_policy* policy, const double* d_sensors,
  *                kinematics and lands when it reaches z <= 0 moving down (its z is set to 0).
  *   trunk        a = sum f / m - g, wd = I^-1 (R' sum r x f - w x I w), semi-implicit Euler in `substeps`
  *                substeps per tick with the torque row held; the quaternion is renormalised every substep.
- * Left out: leg mass, the swing legs' reaction on the trunk, foot slip, terrain, joint limits, and impact
- * dynamics beyond zeroing the landing foot's velocity.  Only the feet touch the ground: a trunk that sinks to
- * min_height is reported as fallen, it does not come to rest.  Binary64, multiplies and adds not contracted,
- * in the statement order of tests/plant_reference.py.                                                    */
+ * mpcqp_plant_step_terrain_device (below) replaces the flat ground by a per-robot inclined plane with its own
+ * friction coefficient.
+ * Left out: leg mass, the swing legs' reaction on the trunk, foot slip, height fields and steps, trunk-ground
+ * contact, joint limits, and impact dynamics beyond zeroing the landing foot's velocity.  Only the feet touch
+ * the ground: a trunk that sinks to min_height is reported as fallen, it does not come to rest.  Binary64,
+ * multiplies and adds not contracted, in the statement order of tests/plant_reference.py.                  */
 typedef struct mpcqp_plant_params {
   double rho_fix[4][5];         /* leg geometry, as mpcqp_est_params (the estimator's kinematics and the       */
   double rho_opt[4][3];         /* plant's agree when these do)                                                */
@@ -929,6 +931,46 @@ int32_t mpcqp_plant_step_wrench_device(const mpcqp_plant_params* pp, double dt, 
                                        const double* d_plant_init, double* d_sensors, double* d_plan_in,
                                        double* d_states, double* d_tq_records, double* d_plant_out, void* stream);
 
+/* ---- inclined ground and per-robot friction.  Terrain row d_terrain [terrain_rows][MPCQP_TR_SIZE]: the ground
+ * of a robot is the plane {p : n.p = d} with its own friction coefficient.                                    */
+#define MPCQP_TR_NORMAL 0        /* [3] unit normal n, world, with n_z > 0                                  */
+#define MPCQP_TR_OFFSET 3        /* d; the ground is {p : n.p = d}                                          */
+#define MPCQP_TR_MU 4            /* friction coefficient (mpcqp_plant_params.mu is not read)                */
+#define MPCQP_TR_SIZE 8          /* 5 used, padded to a multiple of 4 doubles                               */
+
+/* mpcqp_plant_step_wrench_device on the ground of a terrain row.  d_terrain == NULL is
+ * mpcqp_plant_step_wrench_device, bit for bit (and with d_wrench == NULL too, mpcqp_plant_step_device).  With
+ *     hgt(p) = ((n0 p0 + n1 p1) + n2 p2) - d,    dot(n, v) = (n0 v0 + n1 v1) + n2 v2
+ * (contraction off, as everywhere in the plant) exactly four places of the model change and nothing else does:
+ *   1. fresh slot       a foot is held iff hgt(foot) <= 0, and a held foot is put on the plane,
+ *                       foot_k = foot_k - hgt n_k.
+ *   2. ground reaction  with f = -R J^-T tau and fn = dot(n, f): a leg whose fn < 0 lets go.  Otherwise
+ *                       t_k = f_k - fn n_k, ft = sqrt((t0^2 + t1^2) + t2^2), lim = mu fn with the row's mu,
+ *                       sc = ft > lim ? lim / ft : 1, and f_k = fn n_k + sc t_k.
+ *   3. touchdown        a swing foot lands iff hgt(foot) <= 0 && dot(n, v_foot) < 0, and is then put on the
+ *                       plane as in 1.
+ *   4. fallen           status 2.0 iff hgt(pos) < min_height.
+ * The level row n = (0, 0, 1), d = 0, mu = pp->mu gives what the flat ground gives up to the sign of zeros.
+ * Unchanged: a held foot does not slip, and MPCQP_PL_FOOT_FORCE is still the world f_z of a held foot, which
+ * the controller's contact detection thresholds; on the slopes this is meant for (up to 0.3 rad) the cosine
+ * between f_z and the normal force is >= 0.95.  The row is read once per tick and held over its substeps.
+ *   The robot's row: with d_episode_state [batch][MPCQP_ES_SIZE] (the episode stage's slot, read only), robot b
+ * takes row (int) d_episode_state[b][MPCQP_ES_POOL]: the terrain table is parallel to the episode pool, so a
+ * robot's ground restarts with its start pose, and MPCQP_EL_POOL of a log row names the ground the episode ran
+ * on.  With d_episode_state == NULL robot b takes row b, and terrain_rows >= batch is required.  A non-finite
+ * terrain row, or a row index outside [0, terrain_rows), is treated like a non-finite torque row: 3.0 in
+ * MPCQP_PT_STATUS and nothing else written that tick, and nothing is read outside the table.
+ *   MPCQP_ERR_INVALID_ARG, and nothing launched: what mpcqp_plant_step_device rejects; with d_terrain,
+ * terrain_rows < 1, or terrain_rows < batch without d_episode_state.
+ * Left out: height fields and steps, foot slip, trunk-ground contact.  The episode stage's height envelope
+ * (height_min / height_max) stays the world z of the trunk, so a long walk uphill leaves it by height_max:
+ * a caller who walks robots on slopes widens the bounds.                                                    */
+int32_t mpcqp_plant_step_terrain_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                        const double* d_wrench, const double* d_terrain, int32_t terrain_rows,
+                                        const double* d_episode_state, int32_t batch, double* d_plant_state,
+                                        const double* d_plant_init, double* d_sensors, double* d_plan_in,
+                                        double* d_states, double* d_tq_records, double* d_plant_out, void* stream);
+
 /* The stage is stateless: every draw is a function of the Philox key `seed`, the robot index, and
  * MPCQP_ES_EPISODE / MPCQP_ES_TICK of the robot's episode slot, which it only reads.  So a restart needs no
  * zero-fill, and the host can recompute what any logged episode was subjected to.  Philox4x32-10 with
@@ -959,7 +1001,9 @@ int32_t mpcqp_plant_step_wrench_device(const mpcqp_plant_params* pp, double dt, 
  * its sensor row.  Integer and binary64 multiplies and adds only, not contracted, no libm call, in the
  * statement order of tests/disturb_reference.py: the two agree bitwise.
  * Left out: noise on the quaternion and on MPCQP_PL_FOOT_FORCE (the plant writes the foot force in place and two
- * stages read it), the payload's inertia, per-robot plant mass and friction, terrain, foot slip.             */
+ * stages read it), the payload's inertia, per-robot plant mass, foot slip.  (Per-robot friction and inclined
+ * ground are rows of mpcqp_plant_step_terrain_device, chosen per episode through the pool index, not drawn
+ * here; height fields and steps are left out there.)                                                        */
 #define MPCQP_DS_JOINT_POS 0     /* indices of mpcqp_disturb_params.sigma                                  */
 #define MPCQP_DS_JOINT_VEL 1
 #define MPCQP_DS_IMU_ACC 2

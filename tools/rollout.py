@@ -27,6 +27,17 @@ and, with the disturbance stage as the tick's first stage (ControlTick(disturb=)
   full_noise sensor noise NOISE_SIGMA (joint angles, joint rates, accelerometer, gyro) and IMU biases up to
              NOISE_BIAS per axis, redrawn every episode
 
+and, with the plant's ground as a terrain table parallel to the pool (ControlTick(terrain=): a robot's ground and
+friction restart with its start pose), three more:
+
+  mpc_slope  the mpc_ep setup standing slope-parallel on a grid of SLOPE_GRID x SLOPE_GRID pitch / roll angles in
+             +-SLOPE_MAX rad at mu 0.6, the envelope widened to hold the tilted stance
+  full_slope the full_walk setup (standing, then WALK_VX m/s forward from episode tick WALK_AT) on the same pool, the
+             height envelope widened by SLOPE_HEIGHT for the climb.  Its line carries, per pool row, the median
+             MPCQP_PO_ANGLE (the plan stage's filtered terrain pitch) of the robots on that row after the last replay
+             beside the ground's pitch along each robot's heading, and the root_euler_d[1] the plan stage wrote
+  full_mu    the full_walk setup on level ground whose mu is MU_SET[row % 4]; its line carries the end reasons per mu
+
 These report episodes completed, the end-reason histogram, ticks/s and medians of the logged episodes' metrics
 from the device's totals and log, read once after the last replay; they never rerun with a read per tick.
 
@@ -135,10 +146,23 @@ def episode_pool(P, q_leg, tilt, seed, height=None):
     return mpcqp.pack_episode_pool(init, np.stack([zero, zero, e[:, 2]], 1), np.stack([zero, zero, z], 1))
 
 
-EPISODE_FORMS = ("mpc_ep", "full_ep", "full_walk", "servo_ep", "full_push", "full_noise")
+EPISODE_FORMS = ("mpc_ep", "full_ep", "full_walk", "servo_ep", "full_push", "full_noise", "mpc_slope", "full_slope",
+                 "full_mu")
+SLOPE_GRID, SLOPE_MAX, SLOPE_MU, SLOPE_HEIGHT, MU_SET = 5, 0.2, 0.6, 0.25, (0.2, 0.4, 0.6, 0.8)
 PUSH_START, PUSH_TICKS, PUSH_FORCE, PUSH_DIRS, PUSH_BIN = 100, 40, (0.0, 300.0), 16, 25.0
 NOISE_SIGMA, NOISE_BIAS = (0.005, 0.1, 0.2, 0.02), (0.1, 0.01)
 POOL, MAX_TICKS, WALK_AT, WALK_VX = 64, 500, 100, 0.3
+
+
+def slope_pool(q_leg, seed):
+    """(pool rows, terrain rows) of the slope forms: the stance q_leg at a random yaw, slope-parallel on each plane of
+    the pitch / roll grid through the origin; root_euler_d the slope-parallel angles, root_pos_d the start."""
+    a = np.linspace(-SLOPE_MAX, SLOPE_MAX, SLOPE_GRID)
+    pitch, roll = (g.ravel() for g in np.meshgrid(a, a, indexing="ij"))
+    terrain = mpcqp.terrain_from_slope(pitch, roll, SLOPE_MU)
+    flat, _ = start_rows(pitch.size, q_leg, 0.0, seed)
+    init, euler = mpcqp.place_on_terrain(flat, terrain)
+    return mpcqp.pack_episode_pool(init, euler, init[:, :3]), terrain
 
 
 def make_episode(form, B, seed):
@@ -168,8 +192,22 @@ def make_episode(form, B, seed):
                         command=mpcqp.default_command_params()), True
     over = dict(height_min=stand - 0.05, height_max=stand + 0.05)
     scripts = None
-    if form == "full_walk":
-        over = {}
+    tilt_max = 0.3
+    if form in ("mpc_slope", "full_slope"):
+        # the envelope is the world's: the tilt of the steepest ground is added to the bound, and the trunk stands
+        # lower by the ground's cosine (and climbs or descends while it walks)
+        pool, terrain = slope_pool([0.0, 0.8, -1.6] if form == "mpc_slope" else full_stance()[0], seed)
+        if form == "mpc_slope":
+            stand = float(np.median(pool[:, 2]))
+            kw, comp = {}, False
+        tilt_max = 0.3 + float(np.arccos(terrain[:, 2].min()))
+        grow = SLOPE_HEIGHT if form == "full_slope" else 0.0
+        over = dict(height_min=stand * float(terrain[:, 2].min()) - 0.05 - grow, height_max=stand + 0.05 + grow)
+        kw["terrain"] = terrain
+    if form == "full_mu":
+        kw["terrain"] = mpcqp.pack_terrain(np.tile([0.0, 0.0, 1.0], (POOL, 1)), 0.0, np.array(MU_SET)[np.arange(POOL) % 4])
+    if form in ("full_walk", "full_slope", "full_mu"):
+        over = {} if form != "full_slope" else over
         scripts = mpcqp.pack_episode_scripts([[(0, (0, 0, 0), (0, 0, 0), False),
                                                (WALK_AT, (WALK_VX, 0, 0), (0, 0, 0), True)]])
     if form == "full_push":
@@ -181,7 +219,7 @@ def make_episode(form, B, seed):
     elif form == "full_noise":
         kw.update(disturb=mpcqp.default_disturb_params(seed=seed, sigma=NOISE_SIGMA, bias_acc=NOISE_BIAS[0],
                                                        bias_gyro=NOISE_BIAS[1]))
-    ep = mpcqp.default_episode_params(max_ticks=MAX_TICKS, tilt_max=0.3, seed=seed, **over)
+    ep = mpcqp.default_episode_params(max_ticks=MAX_TICKS, tilt_max=tilt_max, seed=seed, **over)
     k = ControlTick(B, dt=DT, plant=pp, episode=ep, episode_pool=pool, episode_scripts=scripts, episode_log_len=8,
                     **kw)
     caller_rows(k, B, np.zeros((B, 3)), np.zeros(B), comp)  # the constants; the stage writes the desired values
@@ -211,7 +249,7 @@ def run_episode(form, B, T, seed):
         robot = np.repeat(np.arange(B), k.episode_log.shape[1])[log["length"] > 0]
         log = log[log["length"] > 0]
         r = {"form": form, "batch": B, "ticks": T, "dt": DT, "ticks_per_s": T / (ms * 1e-3),
-             "robot_ticks_per_s": B * T / (ms * 1e-3), "ms_per_tick": ms / T, "max_ticks": MAX_TICKS, "pool": POOL,
+             "robot_ticks_per_s": B * T / (ms * 1e-3), "ms_per_tick": ms / T, "max_ticks": MAX_TICKS, "pool": int(k.episode_pool.shape[0]),
              "episodes": int(tot["episodes"].sum()), "episode_ticks": int(tot["ticks"].sum()),
              "end_reasons": {n: int(c) for n, c in zip(me.END_NAMES, tot["reason"].sum(0))},
              "robots_running_at_the_end": int((es["phase"] == 1.0).sum()),
@@ -229,7 +267,9 @@ def run_episode(form, B, T, seed):
                     r.update(push_curve(k, robot, log))
                 if form == "full_noise":
                     r.update({"noise_sigma": list(NOISE_SIGMA), "noise_bias": list(NOISE_BIAS)})
-                if form == "full_walk":
+                if form in ("mpc_slope", "full_slope", "full_mu"):
+                    r.update(terrain_report(form, k, es, log))
+                if form in ("full_walk", "full_slope", "full_mu"):
                     d = log["end"][:, :2] - log["start"][:, :2]
                     yaw = log["start"][:, 2]
                     fwd = d[:, 0] * np.cos(yaw) + d[:, 1] * np.sin(yaw)
@@ -246,6 +286,43 @@ def run_episode(form, B, T, seed):
         if extra is not None:
             extra.close()
     return r
+
+
+def terrain_report(form, k, es, log):
+    """Per terrain row (full_mu: per mu): the logged episodes and their end reasons; for full_slope also the median
+    MPCQP_PO_ANGLE of the robots that run on the row after the last replay beside the ground's pitch along their
+    heading, atan((n_x cos yaw + n_y sin yaw) / n_z) (positive: nose down, as root_euler[1])."""
+    from mpcqp import episode as me
+    terrain = k.terrain.cpu().numpy()
+    n = terrain[:, :3]
+    key = terrain[:, _lib.TR_MU] if form == "full_mu" else np.arange(terrain.shape[0])
+    lrow, rrow = log["pool"].astype(int), es["pool"].astype(int)
+    running = es["phase"] == 1.0
+    if form == "full_slope":
+        angle = np.frombuffer(k.plan_out.cpu().numpy().tobytes(), dtype=mpcqp.PLAN_OUT_DTYPE)["terrain_pitch_angle"]
+        yaw = k.plant_out.cpu().numpy()[:, _lib.PT_EULER + 2]
+        along = np.arctan((n[rrow, 0] * np.cos(yaw) + n[rrow, 1] * np.sin(yaw)) / n[rrow, 2])
+        walking = running & (es["tick"] > WALK_AT + 100)
+        pitch_d = k.states.cpu().numpy()[:, _lib.ST_EULER_D + 1]  # what the plan stage made of the angle
+    rows = []
+    for v in np.unique(key):
+        m = np.isin(lrow, np.nonzero(key == v)[0])
+        row = {"episodes": int(m.sum()), "length_median": float(np.median(log["length"][m])) if m.any() else None,
+               "end_reasons": {nm: int((log["reason"][m] == i).sum()) for i, nm in enumerate(me.END_NAMES)}}
+        if form == "full_mu":
+            row["mu"] = float(v)
+        else:
+            row.update(row=int(v), normal=[float(x) for x in n[int(v)]])
+        if form == "full_slope":
+            w = walking & (rrow == v)
+            row.update(robots_walking=int(w.sum()),
+                       po_angle_median=float(np.median(angle[w])) if w.any() else None,
+                       ground_pitch_along_heading_median=float(np.median(along[w])) if w.any() else None,
+                       euler_d_pitch_median=float(np.median(pitch_d[w])) if w.any() else None,
+                       euler_d_sign_agrees_share=float(np.mean(np.sign(pitch_d[w]) == np.sign(along[w])))
+                       if w.any() else None)
+        rows.append(row)
+    return {"terrain_rows": rows}
 
 
 def push_curve(k, robot, log):

@@ -4,6 +4,12 @@ graph-replayed control tick with and without it (HIP events, 3 warm-up runs, med
   plant_kernel_substeps{1,4}_ms   one launch, a standing fleet under weight-bearing torques (every leg in
                                   stance: the inverse kinematics and three 3x3 solves per leg and substep)
   plant_kernel_swing_substeps4_ms the same fleet in free fall (every leg in swing)
+  plant_kernel_{wrench,terrain,wrench_terrain}_substeps4_ms
+                                  the other three instantiations on the standing fleet, in the same session: a zero
+                                  wrench row, and a level terrain row per robot with the plant's mu (the same
+                                  motion, so the four differ by their code alone)
+  plant_kernel_slope_substeps4_ms the terrain instantiation with the fleet standing slope-parallel on planes of
+                                  pitch and roll in +-0.2 rad
   tick_graph_mpc_plant            ControlTick(plant=), MPC-only and truth-fed, closing its own loop
   tick_graph_mpc                  the same tick object captured without its last stage (what the tick enqueued
                                   before the stage existed).  Each repetition snapshots every buffer of the tick,
@@ -14,7 +20,9 @@ graph-replayed control tick with and without it (HIP events, 3 warm-up runs, med
 
 The stage's share of the tick is the median of the 20 paired differences over the median tick without it;
 each form also prints the quartiles and extremes of its 20 repetitions.
-usage: python tools/time_plant.py [--batch 4096]"""
+usage: python tools/time_plant.py [--batch 4096] [--kernels-only] [--flat-only]
+(--kernels-only: the plant kernel's lines alone; --flat-only: without the terrain instantiations, for an A/B against a
+library from before they existed, given by MPCQP_LIB)"""
 import argparse
 import json
 import os
@@ -38,13 +46,17 @@ from time_estimator import RUNS, WARMUP, median_ms  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
-    B = ap.parse_args().batch
+    ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--flat-only", action="store_true")
+    args = ap.parse_args()
+    B = args.batch
     f64 = dict(dtype=torch.float64, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
     out = {"batch": B, "warmup": WARMUP, "runs": RUNS}
 
     # ---- the kernel alone ----
-    def plant_alone(substeps, stance):
+    def plant_alone(substeps, stance, wrench=False, terrain=None):
+        """terrain: None, "level" or "slope"; with either the launch goes through the terrain entry point."""
         pp = mpcqp.default_plant_params(substeps=substeps)
         slot = torch.zeros((B, mpcqp.plant_state_size()), **f64)
         rows = {n: torch.zeros((B, w), **f64) for n, w in (("sn", _lib.SN_SIZE), ("pl", _lib.PL_SIZE),
@@ -57,16 +69,36 @@ def main():
             init = torch.from_numpy(mpcqp.pack_plant_init(pos, np.tile([1.0, 0, 0, 0], (B, 1)),
                                                           np.tile(list(pp.default_joint_pos), (B, 1)))).cuda()
 
+        wr = torch.zeros((B, mpcqp.disturb.PW_SIZE), **f64) if wrench else None
+        tr = None
+        if terrain is not None:
+            rng = np.random.default_rng(5)
+            a = 0.2 if terrain == "slope" else 0.0
+            t_rows = mpcqp.terrain_from_slope(rng.uniform(-a, a, B), rng.uniform(-a, a, B), pp.mu)
+            flat, _ = start_rows(B, list(pp.default_joint_pos)[:3], 0.0, 2)
+            init = torch.from_numpy(mpcqp.place_on_terrain(flat, t_rows)[0]).cuda()
+            tr = torch.from_numpy(t_rows).cuda()
+        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        out_rows = (rows["sn"].data_ptr(), rows["pl"].data_ptr(), rows["st"].data_ptr(), rows["tq"].data_ptr(),
+                    rows["po"].data_ptr(), stream)
+
         def step():
-            mpcqp.plant_step_device(pp, DT, tau.data_ptr(), B, slot.data_ptr(), init.data_ptr() if init is not None else 0,
-                                    rows["sn"].data_ptr(), rows["pl"].data_ptr(), rows["st"].data_ptr(),
-                                    rows["tq"].data_ptr(), rows["po"].data_ptr(), stream)
+            if tr is not None:
+                mpcqp.plant_step_terrain_device(pp, DT, tau.data_ptr(), ptr(wr), tr.data_ptr(), B, 0, B,
+                                                slot.data_ptr(), ptr(init), *out_rows)
+            elif wr is not None:
+                mpcqp.plant_step_wrench_device(pp, DT, tau.data_ptr(), wr.data_ptr(), B, slot.data_ptr(), ptr(init),
+                                               *out_rows)
+            else:
+                mpcqp.plant_step_device(pp, DT, tau.data_ptr(), B, slot.data_ptr(), ptr(init), *out_rows)
 
         step()  # initialise
         torch.cuda.synchronize()
-        if stance:  # tau = J^T (-(0, 0, m g / 4)) at identity attitude, held for the 23 timed ticks
+        if stance:  # tau = J^T (-R^T (0, 0, m g / 4)), held for the 23 timed ticks (R = 1 on level ground)
             J = rows["tq"][:, _lib.TQ_JFOOT:_lib.TQ_JFOOT + 36].reshape(B, 4, 3, 3)
-            tau.copy_((-J[:, :, 2, :] * (pp.mass * pp.gravity / 4.0)).reshape(B, 12))
+            R = rows["st"][:, _lib.ST_ROT:_lib.ST_ROT + 9].reshape(B, 3, 3)
+            fb = R[:, 2, :] * (pp.mass * pp.gravity / 4.0)  # R^T e_z
+            tau.copy_((-torch.einsum("blji,bj->bli", J, fb)).reshape(B, 12))
         ms = median_ms(step)
         po = rows["po"].cpu().numpy()
         assert np.all(po[:, _lib.PT_STATUS] == 0.0)
@@ -76,6 +108,14 @@ def main():
     out["plant_kernel_substeps1_ms"] = plant_alone(1, True)
     out["plant_kernel_substeps4_ms"] = plant_alone(4, True)
     out["plant_kernel_swing_substeps4_ms"] = plant_alone(4, False)
+    out["plant_kernel_wrench_substeps4_ms"] = plant_alone(4, True, wrench=True)
+    if not args.flat_only:
+        out["plant_kernel_terrain_substeps4_ms"] = plant_alone(4, True, terrain="level")
+        out["plant_kernel_wrench_terrain_substeps4_ms"] = plant_alone(4, True, wrench=True, terrain="level")
+        out["plant_kernel_slope_substeps4_ms"] = plant_alone(4, True, terrain="slope")
+    if args.kernels_only:
+        print(json.dumps(out))
+        return
 
     # ---- the two neighbours it shares its thread mapping with ----
     J, fkin, contacts, f_grf = torque_inputs(B, 1)
