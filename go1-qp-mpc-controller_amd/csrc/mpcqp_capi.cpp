@@ -923,6 +923,25 @@ int32_t mpcqp_plant_step_terrain_device(const mpcqp_plant_params* pp, double dt,
              : MPCQP_ERR_HIP;
 }
 
+int32_t mpcqp_plant_step_field_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                      const double* d_wrench, const double* d_field, int32_t field_rows,
+                                      const double* d_heights, int32_t heights_len, const double* d_episode_state,
+                                      int32_t batch, double* d_plant_state, const double* d_plant_init,
+                                      double* d_sensors, double* d_plan_in, double* d_states, double* d_tq_records,
+                                      double* d_plant_out, void* stream) {
+  if (!pp || batch < 0 || !(dt > 0.0) || !isfinite(dt)) return MPCQP_ERR_INVALID_ARG;
+  if (pp->substeps < 1 || pp->substeps > 16) return MPCQP_ERR_INVALID_ARG;
+  if (batch > 0 && (!d_joint_torques || !d_plant_state)) return MPCQP_ERR_INVALID_ARG;
+  if (d_field && (field_rows < 1 || (!d_episode_state && field_rows < batch) || !d_heights || heights_len < 4))
+    return MPCQP_ERR_INVALID_ARG;
+  if (batch == 0) return MPCQP_OK;
+  return mpcqp::launch_plant_field(*pp, dt, d_joint_torques, d_wrench, d_field, field_rows, d_heights, heights_len,
+                                   d_episode_state, batch, d_plant_state, d_plant_init, d_sensors, d_plan_in,
+                                   d_states, d_tq_records, d_plant_out, stream) == hipSuccess
+             ? MPCQP_OK
+             : MPCQP_ERR_HIP;
+}
+
 void mpcqp_disturb_default_params(mpcqp_disturb_params* p) {
   if (!p) return;
   p->load_mass_max = 0.0;

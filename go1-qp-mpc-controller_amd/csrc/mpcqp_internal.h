@@ -145,6 +145,12 @@ hipError_t launch_plant_terrain(const mpcqp_plant_params& pp, double dt, const d
                                 const double* terrain, int terrain_rows, const double* episode_state, int batch,
                                 double* slots, const double* init, double* sensors, double* plan_in, double* states,
                                 double* tq, double* out, void* stream);
+// the same on the bilinear height field of a header table and a heights array (field != nullptr), two more
+// instantiations; the row is chosen as the terrain row is
+hipError_t launch_plant_field(const mpcqp_plant_params& pp, double dt, const double* torques, const double* wrench,
+                              const double* field, int field_rows, const double* heights, int heights_len,
+                              const double* episode_state, int batch, double* slots, const double* init,
+                              double* sensors, double* plan_in, double* states, double* tq, double* out, void* stream);
 
 // Disturbance stage: pushes, payload weight, sensor noise and IMU biases drawn on the device (mpcqp_disturb.hip)
 hipError_t launch_disturb(const mpcqp_disturb_params& dp, const mpcqp_disturb_buffers& bf, int batch, void* stream);

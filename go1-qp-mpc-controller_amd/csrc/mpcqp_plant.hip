@@ -7,10 +7,11 @@
 // tau = J^T (-f_grf)), joint-space swing legs that exert nothing on the trunk, flat ground z = 0,
 // semi-implicit Euler in `substeps` substeps per tick; optionally two external forces on the trunk (the wrench
 // row of mpcqp_plant_step_wrench_device), and optionally a per-robot inclined ground with its own friction
-// coefficient (the terrain row of mpcqp_plant_step_terrain_device).  A held foot does not slip.  Left out: leg
-// mass, the swing legs' reaction on the trunk, foot slip, height fields and steps, trunk-ground contact, joint
-// limits, and impact dynamics beyond zeroing the landing foot's velocity.  The joint inertias are the model's
-// own choice, not identified from a robot description.
+// coefficient (the terrain row of mpcqp_plant_step_terrain_device), or a bilinear height field: steps, stairs,
+// rough ground (the header row and the tile of mpcqp_plant_step_field_device).  A held foot does not slip.  Left
+// out: leg mass, the swing legs' reaction on the trunk, foot slip, overhangs, a riser's vertical face as anything
+// but one steep cell, trunk-ground contact, joint limits, and impact dynamics beyond zeroing the landing foot's
+// velocity.  The joint inertias are the model's own choice, not identified from a robot description.
 //
 // One thread per (robot, leg); the four legs of a robot are the four lanes of one DPP quad, 16 robots
 // per wave (as mpcqp_torque.hip and mpcqp_legplan.hip).  The trunk state is held, and its update is
@@ -188,12 +189,60 @@ __device__ __forceinline__ double hgt(const Ground& t, const double (&p)[3]) {
   return dot(t, p) - t.d;
 }
 
+// The ground of a height-field header row: the tile H[ny][nx] (x the fast index) with node (i, j) at
+// (x0 + i cell, y0 + j cell), friction mu.  The row was checked before this is filled: the tile lies inside the
+// heights array.
+struct Field {
+  double x0, y0, cell, mu;
+  int nx, ny;
+  const double* H;
+};
+// The cell index along one axis and the position inside it.  The clamp is on the double, before the conversion:
+// whatever u is (NaN and +-inf included) the index lies in [0, n - 2].
+__device__ __forceinline__ int field_cell(double u, int n, double& f_raw) {
+#pragma clang fp contract(off)
+  double c = floor(u);
+  c = c > 0.0 ? c : 0.0;  // a NaN ends as 0
+  const double hi = (double)(n - 2);
+  c = c < hi ? c : hi;
+  f_raw = u - c;
+  return (int)c;
+}
+// hgt(p) and the normal n under p, in the grouping of the statement (include/mpcqp.h).  The four corner loads
+// are one batch: their addresses depend on p and the header alone.
+__device__ __forceinline__ double field_lookup(const Field& fd, const double (&p)[3], double (&n)[3]) {
+#pragma clang fp contract(off)
+  double fu_raw, fv_raw;
+  const int i = field_cell((p[0] - fd.x0) / fd.cell, fd.nx, fu_raw);
+  const int j = field_cell((p[1] - fd.y0) / fd.cell, fd.ny, fv_raw);
+  const double* c = fd.H + ((size_t)j * fd.nx + i);
+  const double h00 = c[0], h10 = c[1], h01 = c[fd.nx], h11 = c[fd.nx + 1];
+  const double fu = fmin(fmax(fu_raw, 0.0), 1.0), fv = fmin(fmax(fv_raw, 0.0), 1.0);
+  const double d0 = h10 - h00, d1 = h11 - h01;
+  const double a = h00 + fu * d0;
+  const double b = h01 + fu * d1;
+  const double ba = b - a;
+  const double h = a + fv * ba;
+  const double gx = (fu_raw < 0.0 || fu_raw > 1.0) ? 0.0 : (d0 + fv * (d1 - d0)) / fd.cell;
+  const double gy = (fv_raw < 0.0 || fv_raw > 1.0) ? 0.0 : ba / fd.cell;
+  const double s = sqrt((gx * gx + gy * gy) + 1.0);
+  n[0] = (-gx) / s;
+  n[1] = (-gy) / s;
+  n[2] = 1.0 / s;
+  return (p[2] - h) * n[2];
+}
+
+enum : int { FLAT = 0, PLANE = 1, FIELD = 2 };
+
 // WRENCH: the external forces of a wrench row act on the trunk (include/mpcqp.h has the statement).  Without it
 // the row is never read, and the instantiation is the kernel as it was before the wrench existed.
-// TERRAIN: the ground is the inclined plane of the robot's terrain row, with the row's friction coefficient: the
-// four places marked "terrain" below (include/mpcqp.h has the statement).  Without it neither the table nor the
-// episode slot is read, and the instantiation is the kernel as it was before the terrain existed.
-template <bool WRENCH, bool TERRAIN>
+// GROUND == PLANE: the ground is the inclined plane of the robot's terrain row, with the row's friction coefficient:
+// the four places marked "terrain" below (include/mpcqp.h has the statement).  GROUND == FLAT: neither the table
+// nor the episode slot is read, and the instantiation is the kernel as it was before the terrain existed.
+// GROUND == FIELD: `terrain` is the table of header rows, and at the same four places every point has the hgt and
+// the normal of its own lookup in its tile of `heights`; a held foot's normal is looked up again each substep (the
+// foot does not move, so it is the same one).  Without FIELD no header and no height is read.
+template <bool WRENCH, int GROUND>
 __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp, const double dt,
                                                     const double* __restrict__ torques, const int batch,
                                                     double* __restrict__ slots, const double* __restrict__ init,
@@ -201,8 +250,10 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
                                                     double* __restrict__ states, double* __restrict__ tq,
                                                     double* __restrict__ out, const double* __restrict__ wrench,
                                                     const double* __restrict__ terrain, const int terrain_rows,
-                                                    const double* __restrict__ episode_state) {
+                                                    const double* __restrict__ episode_state,
+                                                    const double* __restrict__ heights, const int heights_len) {
 #pragma clang fp contract(off)
+  constexpr bool TERRAIN = GROUND == PLANE;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = gid >> 2, leg = gid & 3;
   if (b >= batch) return;  // whole quads leave together
@@ -246,6 +297,34 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
       finite = finite && __builtin_isfinite(gr.n[0]) && __builtin_isfinite(gr.n[1]) && __builtin_isfinite(gr.n[2]) &&
                __builtin_isfinite(gr.d) && __builtin_isfinite(gr.mu);
     }
+  }
+  // the header row, chosen as the terrain row is.  A row that is non-finite, or whose tile is degenerate or not
+  // inside the heights array, is a non-finite row too: no height is read for it.
+  Field fd = {0.0, 0.0, 1.0, pp.mu, 2, 2, heights};
+  if constexpr (GROUND == FIELD) {
+    double idx = (double)b;
+    if (episode_state) idx = episode_state[(size_t)MPCQP_ES_SIZE * b + MPCQP_ES_POOL];
+    const bool inside = idx > -1.0 && idx < (double)terrain_rows;
+    finite = finite && inside;
+    if (inside) {
+      const double* hr = terrain + (size_t)MPCQP_HF_SIZE * (int)idx;
+      fd.x0 = hr[MPCQP_HF_X0];
+      fd.y0 = hr[MPCQP_HF_Y0];
+      fd.cell = hr[MPCQP_HF_CELL];
+      fd.mu = hr[MPCQP_HF_MU];
+      const double nx = hr[MPCQP_HF_NX], ny = hr[MPCQP_HF_NY], off = hr[MPCQP_HF_OFFSET];
+      const bool good = __builtin_isfinite(fd.x0) && __builtin_isfinite(fd.y0) && __builtin_isfinite(fd.cell) &&
+                        __builtin_isfinite(fd.mu) && __builtin_isfinite(nx) && __builtin_isfinite(ny) &&
+                        __builtin_isfinite(off) && fd.cell > 0.0 && nx >= 2.0 && ny >= 2.0 && off >= 0.0 &&
+                        off + nx * ny <= (double)heights_len;
+      finite = finite && good;
+      if (good) {  // (nx, ny >= 2 and nx ny <= heights_len: all three fit an int)
+        fd.nx = (int)nx;
+        fd.ny = (int)ny;
+        fd.H = heights + (size_t)off;
+      }
+    }
+    gr.mu = fd.mu;
   }
   if (quad_any(!finite)) {
     if (o && leg == 0) o[MPCQP_PT_STATUS] = 3.0;
@@ -306,7 +385,15 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
     }
     s.st = false;
     kinematics(g, s, R, p_b, J);  // as a swing leg: the foot from the joints
-    if constexpr (TERRAIN) {  // terrain 1: held iff on or under the plane, and put on it
+    if constexpr (GROUND == FIELD) {  // field 1: held iff on or under the surface, and put on it
+      double n[3];
+      const double hf = field_lookup(fd, s.foot, n);
+      s.st = hf <= 0.0;
+      if (s.st) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s.foot[k] = s.foot[k] - hf * n[k];
+      }
+    } else if constexpr (TERRAIN) {  // terrain 1: held iff on or under the plane, and put on it
       const double hf = hgt(gr, s.foot);
       s.st = hf <= 0.0;
       if (s.st) {
@@ -350,7 +437,10 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
         }
         lu3_solve(At, bt, gl);
         mat_vec(R, gl, fw);
-        if constexpr (TERRAIN) {  // terrain 2: the normal part decides, the tangential part is scaled onto the cone
+        if constexpr (GROUND == FIELD) {  // field 2: terrain 2 with the normal under the held foot
+          field_lookup(fd, s.foot, gr.n);
+        }
+        if constexpr (GROUND != FLAT) {  // terrain 2: the normal part decides, the tangential part is scaled onto the cone
           const double fg[3] = {-fw[0], -fw[1], -fw[2]};
           const double fn = dot(gr, fg);
           if (fn < 0.0) {
@@ -465,12 +555,17 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
         mat_vec(J2, s.qd, jq);
 #pragma unroll
         for (int k = 0; k < 3; ++k) u[k] = wp[k] + jq[k];
-        if constexpr (TERRAIN) {  // terrain 3: lands on or under the plane while moving into it
+        if constexpr (GROUND != FLAT) {  // terrain 3: lands on or under the ground while moving into it
           double ru[3], fv[3];
           mat_vec(R2, u, ru);
 #pragma unroll
           for (int k = 0; k < 3; ++k) fv[k] = s.v[k] + ru[k];
-          const double hf = hgt(gr, s.foot);
+          double hf;
+          if constexpr (GROUND == FIELD) {  // field 3: hgt and the normal under the swing foot
+            hf = field_lookup(fd, s.foot, gr.n);
+          } else {
+            hf = hgt(gr, s.foot);
+          }
           if (hf <= 0.0 && dot(gr, fv) < 0.0) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) s.foot[k] = s.foot[k] - hf * gr.n[k];
@@ -498,7 +593,10 @@ __global__ __launch_bounds__(256) void plant_kernel(const mpcqp_plant_params pp,
     return;
   }
   double status;
-  if constexpr (TERRAIN) {  // terrain 4: the trunk's height over the plane
+  if constexpr (GROUND == FIELD) {  // field 4: the trunk's height over the ground under it
+    double n[3];
+    status = field_lookup(fd, s.pos, n) < pp.min_height ? 2.0 : 0.0;
+  } else if constexpr (TERRAIN) {  // terrain 4: the trunk's height over the plane
     status = hgt(gr, s.pos) < pp.min_height ? 2.0 : 0.0;
   } else {
     status = s.pos[2] < pp.min_height ? 2.0 : 0.0;
@@ -631,9 +729,10 @@ hipError_t launch_plant(const mpcqp_plant_params& pp, double dt, const double* t
                         const double* init, double* sensors, double* plan_in, double* states, double* tq,
                         double* out, void* stream) {
   const int threads = 4 * batch;
-  hipLaunchKernelGGL((plant::plant_kernel<false, false>), dim3((threads + 255) / 256), dim3(256), 0,
+  hipLaunchKernelGGL((plant::plant_kernel<false, plant::FLAT>), dim3((threads + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, pp, dt, torques, batch, slots, init, sensors, plan_in, states, tq, out,
-                     (const double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr);
+                     (const double*)nullptr, (const double*)nullptr, 0, (const double*)nullptr, (const double*)nullptr,
+                     0);
   return hipGetLastError();
 }
 
@@ -642,9 +741,9 @@ hipError_t launch_plant_wrench(const mpcqp_plant_params& pp, double dt, const do
                                double* states, double* tq, double* out, void* stream) {
   if (!wrench) return launch_plant(pp, dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, stream);
   const int threads = 4 * batch;
-  hipLaunchKernelGGL((plant::plant_kernel<true, false>), dim3((threads + 255) / 256), dim3(256), 0,
+  hipLaunchKernelGGL((plant::plant_kernel<true, plant::FLAT>), dim3((threads + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, pp, dt, torques, batch, slots, init, sensors, plan_in, states, tq, out, wrench,
-                     (const double*)nullptr, 0, (const double*)nullptr);
+                     (const double*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, 0);
   return hipGetLastError();
 }
 
@@ -657,12 +756,32 @@ hipError_t launch_plant_terrain(const mpcqp_plant_params& pp, double dt, const d
   const int threads = 4 * batch;
   const dim3 grid((threads + 255) / 256), block(256);
   if (wrench)
-    hipLaunchKernelGGL((plant::plant_kernel<true, true>), grid, block, 0, (hipStream_t)stream, pp, dt, torques, batch,
-                       slots, init, sensors, plan_in, states, tq, out, wrench, terrain, terrain_rows, episode_state);
+    hipLaunchKernelGGL((plant::plant_kernel<true, plant::PLANE>), grid, block, 0, (hipStream_t)stream, pp, dt, torques, batch,
+                       slots, init, sensors, plan_in, states, tq, out, wrench, terrain, terrain_rows, episode_state,
+                       (const double*)nullptr, 0);
   else
-    hipLaunchKernelGGL((plant::plant_kernel<false, true>), grid, block, 0, (hipStream_t)stream, pp, dt, torques, batch,
+    hipLaunchKernelGGL((plant::plant_kernel<false, plant::PLANE>), grid, block, 0, (hipStream_t)stream, pp, dt, torques, batch,
                        slots, init, sensors, plan_in, states, tq, out, (const double*)nullptr, terrain, terrain_rows,
-                       episode_state);
+                       episode_state, (const double*)nullptr, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_plant_field(const mpcqp_plant_params& pp, double dt, const double* torques, const double* wrench,
+                              const double* field, int field_rows, const double* heights, int heights_len,
+                              const double* episode_state, int batch, double* slots, const double* init,
+                              double* sensors, double* plan_in, double* states, double* tq, double* out, void* stream) {
+  if (!field)
+    return launch_plant_wrench(pp, dt, torques, wrench, batch, slots, init, sensors, plan_in, states, tq, out, stream);
+  const int threads = 4 * batch;
+  const dim3 grid((threads + 255) / 256), block(256);
+  if (wrench)
+    hipLaunchKernelGGL((plant::plant_kernel<true, plant::FIELD>), grid, block, 0, (hipStream_t)stream, pp, dt, torques,
+                       batch, slots, init, sensors, plan_in, states, tq, out, wrench, field, field_rows, episode_state,
+                       heights, heights_len);
+  else
+    hipLaunchKernelGGL((plant::plant_kernel<false, plant::FIELD>), grid, block, 0, (hipStream_t)stream, pp, dt, torques,
+                       batch, slots, init, sensors, plan_in, states, tq, out, (const double*)nullptr, field, field_rows,
+                       episode_state, heights, heights_len);
   return hipGetLastError();
 }
 

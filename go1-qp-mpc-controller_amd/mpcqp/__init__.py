@@ -21,8 +21,9 @@ from .legplan import (PLAN_OUT_DTYPE, PlanParams, default_plan_params, leg_plan_
 from .policy import (POLICY_OUT_DTYPE, POLICY_STATE_DTYPE, Policy, PolicyParams, default_policy_params,
                      load_policy_weights, policy_device, policy_state_size)
 from .plant import (PLANT_OUT_DTYPE, PLANT_STATE_DTYPE, PlantParams, default_plant_params, pack_plant_init,
-                    pack_terrain, place_on_terrain, plant_state_size, plant_step_device, plant_step_terrain_device,
-                    terrain_from_slope, terrain_height)
+                    field_lookup, pack_height_field, pack_terrain, place_on_field, place_on_terrain, plant_state_size,
+                    plant_step_device, plant_step_field_device, plant_step_terrain_device, terrain_from_slope,
+                    terrain_height)
 from .records import (GO1_Q, GO1_R, RobotStates, assemble_compute_grf, assemble_test_mpc,
                       pack_states, synthetic_go1)
 from .robot_control import Go1RobotControl, RobotControl
@@ -44,7 +45,8 @@ __all__ = [
     "load_policy_weights", "policy_device", "policy_state_size",
     "PLANT_OUT_DTYPE", "PLANT_STATE_DTYPE", "PlantParams", "default_plant_params", "pack_plant_init",
     "plant_state_size", "plant_step_device", "pack_terrain", "place_on_terrain", "plant_step_terrain_device",
-    "terrain_from_slope", "terrain_height",
+    "terrain_from_slope", "terrain_height", "field_lookup", "pack_height_field", "place_on_field",
+    "plant_step_field_device",
     "EPISODE_LOG_DTYPE", "EPISODE_STATE_DTYPE", "EPISODE_TOTALS_DTYPE", "EpisodeBuffers", "EpisodeParams",
     "default_episode_params", "episode_buffers", "episode_device", "episode_state_size", "pack_episode_pool",
     "pack_episode_scripts",

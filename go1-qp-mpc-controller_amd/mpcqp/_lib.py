@@ -56,6 +56,8 @@ PT_POS, PT_QUAT, PT_EULER, PT_LIN_VEL, PT_ANG_VEL, PT_CONTACTS, PT_GRF, PT_FOOT,
 PT_STATUS, PT_SIZE = 47, 48
 # terrain row of the plant stage (include/mpcqp.h MPCQP_TR_*)
 TR_NORMAL, TR_OFFSET, TR_MU, TR_SIZE = 0, 3, 4, 8
+# height-field header row of the plant stage (include/mpcqp.h MPCQP_HF_*)
+HF_X0, HF_Y0, HF_CELL, HF_MU, HF_NX, HF_NY, HF_OFFSET, HF_SIZE = 0, 1, 2, 3, 4, 5, 6, 8
 
 
 def rec_feet(N):
@@ -246,7 +248,7 @@ EXPORTED = [
     "mpcqp_episode_state_size", "mpcqp_episode_device",
     "mpcqp_plant_step_wrench_device", "mpcqp_disturb_default_params", "mpcqp_disturb_params_size",
     "mpcqp_disturb_buffers_size", "mpcqp_disturb_device",
-    "mpcqp_plant_step_terrain_device",
+    "mpcqp_plant_step_terrain_device", "mpcqp_plant_step_field_device",
 ]
 
 _libs = {}
@@ -428,6 +430,10 @@ def load(debug=False):
         L.mpcqp_plant_step_terrain_device.argtypes = [ctypes.POINTER(PlantParams), ctypes.c_double, vp, vp, vp, i32, vp,
                                                       i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.mpcqp_plant_step_terrain_device.restype = i32
+    if hasattr(L, "mpcqp_plant_step_field_device"):
+        L.mpcqp_plant_step_field_device.argtypes = [ctypes.POINTER(PlantParams), ctypes.c_double, vp, vp, vp, i32, vp,
+                                                    i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mpcqp_plant_step_field_device.restype = i32
     if L.mpcqp_est_params_size() != ctypes.sizeof(EstimatorParams):
         raise MpcQpError(f"ABI mismatch: mpcqp_est_params is {L.mpcqp_est_params_size()} bytes in C, "
                          f"{ctypes.sizeof(EstimatorParams)} in ctypes")

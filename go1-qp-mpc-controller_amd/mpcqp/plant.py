@@ -3,10 +3,11 @@
 Per robot and per tick the device stage advances a rigid-body model of the robot by one control period
 under the tick's joint torques and writes the next tick's sensor-level rows: a single rigid trunk on
 massless stance legs (a held foot turns the joint torques into the ground reaction f = -R J^-T tau),
-joint-space swing legs, flat ground or (plant_step_terrain_device) a per-robot inclined plane with its own friction
-coefficient, semi-implicit Euler in ``substeps`` substeps.  Left out: leg mass, the swing legs' reaction on the
-trunk, foot slip, height fields and steps, trunk-ground contact, joint limits, and impact dynamics beyond zeroing
-the landing foot's velocity.  The state lives in a per-robot device slot of ``plant_state_size()`` doubles;
+joint-space swing legs, flat ground, (plant_step_terrain_device) a per-robot inclined plane with its own friction
+coefficient or (plant_step_field_device) a bilinear height field of steps, stairs or rough ground, semi-implicit
+Euler in ``substeps`` substeps.  Left out: leg mass, the swing legs' reaction on the trunk, foot slip, overhangs, a
+riser's vertical face as anything but one steep cell, trunk-ground contact, joint limits, and impact dynamics
+beyond zeroing the landing foot's velocity.  The state lives in a per-robot device slot of ``plant_state_size()`` doubles;
 zero-filled = fresh, and zeroing a robot's slots is how a fleet resets a fallen robot (a robot whose status
 is not 0 is frozen until then).  The episode stage (episode.py) does that on the device: it ends a fallen
 robot's episode, zeroes its slots over two ticks and restarts it from a drawn start row.
@@ -16,8 +17,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (PI_JOINT_POS, PI_POS, PI_QUAT, PI_SIZE, TR_MU, TR_NORMAL, TR_OFFSET, TR_SIZE, PlantParams, check, load,
-                   override)
+from ._lib import (HF_CELL, HF_MU, HF_NX, HF_NY, HF_OFFSET, HF_SIZE, HF_X0, HF_Y0, PI_JOINT_POS, PI_POS, PI_QUAT,
+                   PI_SIZE, TR_MU, TR_NORMAL, TR_OFFSET, TR_SIZE, PlantParams, check, load, override)
 
 # the slot (include/mpcqp.h MPCQP_PN_*) and the output row (MPCQP_PT_*)
 PLANT_STATE_DTYPE = np.dtype([
@@ -164,6 +165,149 @@ def _feet_body(pp, q):
     hh = lt * c1 + (le * c12 + a0 * s12)
     xx = (a0 * c12 - le * s12) - lt * s1
     return np.stack([ox + xx, oy + (dd * c0 + hh * s0), dd * s0 - hh * c0], -1)
+
+
+def pack_height_field(tiles, x0, y0, cell, mu, share=None):
+    """Header rows [P, HF_SIZE] (include/mpcqp.h MPCQP_HF_*) and the heights array of the bilinear height-field
+    ground.  ``tiles``: a list of 2-D arrays H[ny][nx] of possibly different shapes, node (i, j) of a row's tile at
+    (x0 + i cell, y0 + j cell).  ``share`` [P]: the tile of each header row, so several rows (start poses) share a
+    tile; None: one row per tile, in order.  ``x0``, ``y0``, ``cell`` and ``mu`` broadcast over the rows.  Raises on a
+    non-finite entry, a tile under 2x2, cell <= 0 and mu < 0 (the device checks the header, not the heights)."""
+    tiles = [np.asarray(t, dtype=np.float64) for t in tiles]
+    for t in tiles:
+        if t.ndim != 2 or t.shape[0] < 2 or t.shape[1] < 2:
+            raise ValueError(f"pack_height_field: a tile needs at least 2x2 nodes, not {t.shape}")
+        if not np.all(np.isfinite(t)):
+            raise ValueError("pack_height_field: non-finite height")
+    which = np.arange(len(tiles)) if share is None else np.asarray(share, dtype=np.int64).reshape(-1)
+    if which.size == 0 or which.min() < 0 or which.max() >= len(tiles):
+        raise ValueError("pack_height_field: share names a tile that is not there")
+    P = which.shape[0]
+    x0, y0, cell, mu = (np.broadcast_to(np.asarray(a, dtype=np.float64), (P,)) for a in (x0, y0, cell, mu))
+    if not all(np.all(np.isfinite(a)) for a in (x0, y0, cell, mu)):
+        raise ValueError("pack_height_field: non-finite entry")
+    if np.any(cell <= 0.0):
+        raise ValueError("pack_height_field: cell must be positive")
+    if np.any(mu < 0.0):
+        raise ValueError("pack_height_field: mu must not be negative")
+    offset = np.concatenate([[0], np.cumsum([t.size for t in tiles])])
+    rows = np.zeros((P, HF_SIZE))
+    rows[:, HF_X0], rows[:, HF_Y0], rows[:, HF_CELL], rows[:, HF_MU] = x0, y0, cell, mu
+    rows[:, HF_NX] = [tiles[k].shape[1] for k in which]
+    rows[:, HF_NY] = [tiles[k].shape[0] for k in which]
+    rows[:, HF_OFFSET] = offset[which]
+    return rows, np.concatenate([t.ravel() for t in tiles])
+
+
+def _field_cell(u, n):
+    """The cell index along one axis, clamped on the double to [0, n - 2], and u - index."""
+    with np.errstate(invalid="ignore"):
+        c = np.floor(u)
+        c = np.where(c > 0.0, c, 0.0)  # (a NaN ends as 0)
+        c = np.where(c < n - 2.0, c, n - 2.0)
+        return c.astype(np.int64), u - c
+
+
+def field_lookup(rows, heights, row_index, p):
+    """(hgt, n) of the world points p [..., 3] over the tiles of the header rows ``row_index`` (an int or an int array
+    that broadcasts against p's leading axes from the left), with the arithmetic of the statement in
+    include/mpcqp.h: hgt [...] = (p_z - h) n_z, the first-order normal distance, and the unit normal n [..., 3]."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, HF_SIZE)
+    H = np.asarray(heights, dtype=np.float64).reshape(-1)
+    p = np.asarray(p, dtype=np.float64)
+    idx = np.asarray(row_index, dtype=np.int64)
+    r = rows[idx.reshape(idx.shape + (1,) * (p.ndim - 1 - idx.ndim))]
+    x0, y0, cell = r[..., HF_X0], r[..., HF_Y0], r[..., HF_CELL]
+    nx, ny, off = r[..., HF_NX], r[..., HF_NY], r[..., HF_OFFSET].astype(np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        i, fu_raw = _field_cell((p[..., 0] - x0) / cell, nx)
+        j, fv_raw = _field_cell((p[..., 1] - y0) / cell, ny)
+        at = off + j * nx.astype(np.int64) + i
+        h00, h10, h01, h11 = H[at], H[at + 1], H[at + nx.astype(np.int64)], H[at + nx.astype(np.int64) + 1]
+        fu, fv = np.minimum(np.maximum(fu_raw, 0.0), 1.0), np.minimum(np.maximum(fv_raw, 0.0), 1.0)
+        d0, d1 = h10 - h00, h11 - h01
+        a = h00 + fu * d0
+        b = h01 + fu * d1
+        ba = b - a
+        h = a + fv * ba
+        gx = np.where((fu_raw < 0.0) | (fu_raw > 1.0), 0.0, (d0 + fv * (d1 - d0)) / cell)
+        gy = np.where((fv_raw < 0.0) | (fv_raw > 1.0), 0.0, ba / cell)
+        s = np.sqrt((gx * gx + gy * gy) + 1.0)
+        n = np.stack([(-gx) / s, (-gy) / s, 1.0 / s], -1)
+        return (p[..., 2] - h) * n[..., 2], n
+
+
+def _ik_body(pp, p):
+    """Joint angles [B,4,3] of body-frame foot positions [B,4,3] and the in-reach flag [B,4]: the inverse kinematics
+    of the plant (csrc/mpcqp_plant.hip ik) on the geometry of ``pp``."""
+    fix = np.array(list(pp.rho_fix), dtype=np.float64).reshape(1, 4, 5)
+    opt = np.array(list(pp.rho_opt), dtype=np.float64).reshape(1, 4, 3)
+    ox, oy, dd, lt, le, a0 = fix[..., 0], fix[..., 1], fix[..., 2] + opt[..., 1], fix[..., 3], fix[..., 4] - opt[..., 2], opt[..., 0]
+    lce, phi = np.sqrt(le * le + a0 * a0), np.arctan2(a0, le)
+    x, y, z = p[..., 0] - ox, p[..., 1] - oy, p[..., 2]
+    with np.errstate(invalid="ignore"):
+        arg = (y * y + z * z) - dd * dd
+        hh = np.sqrt(arg)
+        c = (((x * x + hh * hh) - lt * lt) - lce * lce) / ((2.0 * lt) * lce)
+        qk = -np.arccos(c)
+        q = np.stack([np.arctan2(z, y) - np.arctan2(-hh, dd),
+                      np.arctan2(-x, hh) - np.arctan2(lce * np.sin(qk), lt + lce * np.cos(qk)), qk + phi], -1)
+        return q, (arg >= 0.0) & (np.abs(c) <= 1.0)
+
+
+def place_on_field(init_rows, rows, heights, row_index, pp=None, height=None):
+    """Init rows [B, PI_SIZE] placed as a stance on the height field of the header rows ``row_index`` [B]: the trunk
+    is level at the start row's yaw and x, y, at ``height`` (default: the start row's own z) over the mean ground
+    under the four nominal feet (those of the start row's joint angles); every leg's joint angles come from the
+    plant's inverse kinematics with its foot on the surface under the nominal foot, 5e-16 under it in hgt so that
+    rounding leaves every foot held and none deeper than 1e-15.  Raises if a foot is out of reach.  ``pp``: the
+    PlantParams whose leg geometry places the feet (default: the library's).  Returns the init rows and the
+    (roll, pitch, yaw) [B,3] of the placed attitude, for root_euler_d."""
+    init = np.array(init_rows, dtype=np.float64).reshape(-1, PI_SIZE)
+    B = init.shape[0]
+    idx = np.broadcast_to(np.asarray(row_index, dtype=np.int64), (B,))
+    pp = default_plant_params() if pp is None else pp
+    q0 = init[:, PI_QUAT:PI_QUAT + 4]
+    yaw = np.arctan2(2.0 * (q0[:, 0] * q0[:, 3] + q0[:, 1] * q0[:, 2]), 1.0 - 2.0 * (q0[:, 2] ** 2 + q0[:, 3] ** 2))
+    zero = np.zeros(B)
+    quat = np.stack([np.cos(yaw / 2), zero, zero, np.sin(yaw / 2)], 1)
+    R = _quat_rot(quat)
+    nominal = np.einsum("bij,blj->bli", R, _feet_body(pp, init[:, PI_JOINT_POS:PI_JOINT_POS + 12].reshape(B, 4, 3)))
+    xy = init[:, None, PI_POS:PI_POS + 2] + nominal[..., :2]
+    hf, n = field_lookup(rows, heights, idx, np.concatenate([xy, np.zeros((B, 4, 1))], -1))
+    ground = -hf / n[..., 2]  # h under each nominal foot
+    pos = init[:, PI_POS:PI_POS + 3].copy()
+    pos[:, 2] = ground.mean(1) + (init[:, PI_POS + 2] if height is None else np.broadcast_to(height, (B,)))
+    target = np.concatenate([xy, ground[..., None]], -1)
+    for _ in range(8):
+        q, ok = _ik_body(pp, np.einsum("bji,blj->bli", R, target - pos[:, None]))
+        if not np.all(ok):
+            raise ValueError(f"place_on_field: a foot of robot(s) {np.nonzero(~ok.all(1))[0].tolist()} is out of reach")
+        foot = pos[:, None] + np.einsum("bij,blj->bli", R, _feet_body(pp, q))
+        hf, n = field_lookup(rows, heights, idx, foot)
+        if np.all((hf <= -2e-16) & (hf >= -8e-16)):
+            break
+        target[..., 2] -= (hf + 5e-16) / n[..., 2]
+    else:
+        raise ValueError("place_on_field: the feet did not settle on the surface")
+    out = init.copy()
+    out[:, PI_POS:PI_POS + 3] = pos
+    out[:, PI_QUAT:PI_QUAT + 4] = quat
+    out[:, PI_JOINT_POS:PI_JOINT_POS + 12] = q.reshape(B, 12)
+    return out, np.stack([zero, zero, yaw], 1)
+
+
+def plant_step_field_device(pp, dt, d_torques, d_wrench, d_field, field_rows, d_heights, heights_len, d_episode_state,
+                            batch, d_plant_state, d_init=0, d_sensors=0, d_plan_in=0, d_states=0, d_tq_records=0,
+                            d_plant_out=0, stream=0):
+    """mpcqp_plant_step_field_device on device pointers (ints; 0 for the optional ones, d_wrench, d_field and
+    d_episode_state among them).  Robot b stands on the tile of header row (int) episode_state[b][ES_POOL], or of row
+    b without an episode slot."""
+    check(load().mpcqp_plant_step_field_device(
+        ctypes.byref(pp), float(dt), d_torques or None, d_wrench or None, d_field or None, int(field_rows),
+        d_heights or None, int(heights_len), d_episode_state or None, int(batch), d_plant_state or None,
+        d_init or None, d_sensors or None, d_plan_in or None, d_states or None, d_tq_records or None,
+        d_plant_out or None, stream or None), None, "mpcqp_plant_step_field_device")
 
 
 def plant_step_terrain_device(pp, dt, d_torques, d_wrench, d_terrain, terrain_rows, d_episode_state, batch,

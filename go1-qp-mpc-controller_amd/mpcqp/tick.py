@@ -45,8 +45,8 @@ overwrites the ``torques`` row of the robots whose control type is 2 from ``sens
 ``cmd``.  Robots of type 0 and 1 are untouched by it.
 
 plant (``plant``, a PlantParams; what the reference left to Gazebo): a rigid-body model (single trunk, massless
-stance legs, joint-space swing legs, flat ground or with ``terrain`` a per-robot inclined plane with its own
-friction) moves every robot one control period on under the final ``torques`` row and writes the next tick's ``sensors`` and foot forces, so T replays are a T-tick closed-loop
+stance legs, joint-space swing legs, flat ground, with ``terrain`` a per-robot inclined plane with its own
+friction, or with ``field`` a bilinear height field) moves every robot one control period on under the final ``torques`` row and writes the next tick's ``sensors`` and foot forces, so T replays are a T-tick closed-loop
 rollout with no host write in between.  Without ``estimator`` it also writes the ground truth of the estimator's
 fields into ``states`` / ``plan_in`` / ``tq_records``.
 
@@ -63,7 +63,7 @@ from .episode import (EL_SIZE, ET_SIZE, POOL_INIT, POOL_SIZE, SEG_SIZE, EpisodeP
                       episode_state_size)
 from .estimator import estimator_state_size, state_estimate_device
 from .legplan import leg_plan_typed_device, plan_state_size
-from .plant import plant_state_size, plant_step_device, plant_step_terrain_device
+from .plant import plant_state_size, plant_step_device, plant_step_field_device, plant_step_terrain_device
 from .policy import policy_device, policy_state_size
 from .solver import MpcQpSolver
 from .torques import joint_torques_device
@@ -78,7 +78,7 @@ class ControlTick:
     def __init__(self, batch, params=None, device=0, plan=None, dt=None, estimator=None, command=None,
                  control_type=None, balance=None, gains=None, policy=None, plant=None, plant_init=None,
                  episode=None, episode_pool=None, episode_scripts=None, episode_log_len=4, disturb=None,
-                 disturb_dirs=None, terrain=None):
+                 disturb_dirs=None, terrain=None, field=None):
         """control_type: None = the MPC-only tick; 0 / 1 = every robot takes the balance / the MPC branch;
         2 (with ``policy``) = every robot takes the policy branch;
         "per_robot" = the tick owns ``self.control_type``, an int32 [B] device tensor the caller writes
@@ -109,12 +109,16 @@ class ControlTick:
         owns as ``terrain``: [B, TR_SIZE], robot b on row b, or with ``episode`` [P, TR_SIZE] parallel to
         ``episode_pool``, each robot on the row of its episode's pool index, so the ground restarts with the start
         pose.  ``without=("terrain",)`` gives the tick on flat ground.
+        ``field`` ((rows, heights) of pack_height_field; needs ``plant``, exclusive with ``terrain``): the same kind
+        of option for a bilinear height-field ground (steps, stairs, rough terrain).  The tick then owns ``field``
+        [B, HF_SIZE] (with ``episode`` [P, HF_SIZE], parallel to ``episode_pool``) and ``heights``, the tiles.
+        ``without=("field",)`` gives the tick on flat ground.
         A buffer the tick does not own is an absent attribute (``_buffers`` has the rule)."""
         import torch
         self.torch = torch
         self.B = int(batch)
         o = dict(disturb=disturb, command=command, estimator=estimator, plan=plan, control_type=control_type,
-                 policy=policy, plant=plant, episode=episode, terrain=terrain)
+                 policy=policy, plant=plant, episode=episode, terrain=terrain, field=field)
         tick_dt = self._check(o, dt, episode_pool)
         if tick_dt is not None:
             self.dt = tick_dt
@@ -163,6 +167,15 @@ class ControlTick:
                 raise ValueError(f"ControlTick(terrain=...) has {rows.shape[0]} rows; it needs {want}, one per "
                                  f"{'row of episode_pool' if episode is not None else 'robot'}")
             self.terrain = o["terrain"] = rows.to(dev).contiguous()
+        if field is not None:
+            rows, heights = field
+            rows = given(rows).reshape(-1, _lib.HF_SIZE)
+            want = self.episode_pool.shape[0] if episode is not None else self.B
+            if rows.shape[0] != want:
+                raise ValueError(f"ControlTick(field=...) has {rows.shape[0]} rows; it needs {want}, one per "
+                                 f"{'row of episode_pool' if episode is not None else 'robot'}")
+            self.field = o["field"] = rows.to(dev).contiguous()
+            self.heights = given(heights).reshape(-1).to(dev).contiguous()
         self.counter = torch.zeros((self.B,), dtype=torch.int32, device=dev)
         for name, width in self._buffers(o).items():  # zero = a fresh slot, an uninitialised filter, a reset controller
             if width is not None:
@@ -199,6 +212,10 @@ class ControlTick:
             raise ValueError("ControlTick(disturb=...) needs plant= and episode=")
         if on("terrain") and not on("plant"):
             raise ValueError("ControlTick(terrain=...) needs plant=")
+        if on("field") and not on("plant"):
+            raise ValueError("ControlTick(field=...) needs plant=")
+        if on("field") and on("terrain"):
+            raise ValueError("ControlTick(field=...) and terrain= exclude each other")
         return float(dt) if on("plan") or on("estimator") or on("command") or on("plant") else None
 
     def _buffers(self, o):
@@ -231,6 +248,8 @@ class ControlTick:
             t.update(plant_state=plant_state_size(), plant_out=_lib.PT_SIZE, plant_init=None)
         if "terrain" in on:
             t["terrain"] = None
+        if "field" in on:
+            t.update(field=None, heights=None)
         if "episode" in on:
             t.update(episode_state=episode_state_size(), episode_log=(o["episode"].log_len, EL_SIZE),
                      episode_totals=ET_SIZE, episode_pool=None, episode_scripts=None)
@@ -307,6 +326,10 @@ class ControlTick:
                 st.append(("plant", lambda s: plant_step_terrain_device(
                     o["plant"], dt, p("torques"), p("wrench"), p("terrain"), o["terrain"].shape[0],
                     p("episode_state"), *rows(s))))
+            elif on("field"):
+                st.append(("plant", lambda s: plant_step_field_device(
+                    o["plant"], dt, p("torques"), p("wrench"), p("field"), o["field"].shape[0], p("heights"),
+                    self.heights.numel(), p("episode_state"), *rows(s))))
             elif on("disturb"):
                 st.append(("plant", lambda s: plant_step_wrench_device(
                     o["plant"], dt, p("torques"), p("wrench"), *rows(s))))
@@ -375,7 +398,7 @@ class ControlTick:
         ``without`` (stage names) records instead the tick the constructor would have built had those stages'
         options been None, on the same buffers: without ``disturb`` the estimator and the policy stage read
         ``sensors`` and the plant runs without the wrench row; without ``estimate`` the plant also writes the
-        truth image; without ``terrain`` (an option, not a stage) the plant runs on flat ground.  A combination the constructor rejects raises its ValueError (``plant`` under an episode
+        truth image; without ``terrain`` or ``field`` (options, not stages) the plant runs on flat ground.  A combination the constructor rejects raises its ValueError (``plant`` under an episode
         stage).  Only the full tick's graph becomes ``self.graph``."""
         torch = self.torch
         stages = self._stages_of(without)

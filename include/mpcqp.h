@@ -657,11 +657,12 @@ int32_t mpcqp_policy_device(const mpcqp_policy* policy, const double* d_sensors,
  *   trunk        a = sum f / m - g, wd = I^-1 (R' sum r x f - w x I w), semi-implicit Euler in `substeps`
  *                substeps per tick with the torque row held; the quaternion is renormalised every substep.
  * mpcqp_plant_step_terrain_device (below) replaces the flat ground by a per-robot inclined plane with its own
- * friction coefficient.
- * Left out: leg mass, the swing legs' reaction on the trunk, foot slip, height fields and steps, trunk-ground
- * contact, joint limits, and impact dynamics beyond zeroing the landing foot's velocity.  Only the feet touch
- * the ground: a trunk that sinks to min_height is reported as fallen, it does not come to rest.  Binary64,
- * multiplies and adds not contracted, in the statement order of tests/plant_reference.py.                  */
+ * friction coefficient, and mpcqp_plant_step_field_device by a bilinear height field (steps, stairs, rough ground).
+ * Left out: leg mass, the swing legs' reaction on the trunk, foot slip, overhangs, a riser's vertical face as
+ * anything but one steep cell, trunk-ground contact, joint limits, and impact dynamics beyond zeroing the landing
+ * foot's velocity.  Only the feet touch the ground: a trunk that sinks to min_height is reported as fallen, it does
+ * not come to rest.  Binary64, multiplies and adds not contracted, in the statement order of
+ * tests/plant_reference.py.                                                                                */
 typedef struct mpcqp_plant_params {
   double rho_fix[4][5];         /* leg geometry, as mpcqp_est_params (the estimator's kinematics and the       */
   double rho_opt[4][3];         /* plant's agree when these do)                                                */
@@ -962,7 +963,7 @@ int32_t mpcqp_plant_step_wrench_device(const mpcqp_plant_params* pp, double dt, 
  * MPCQP_PT_STATUS and nothing else written that tick, and nothing is read outside the table.
  *   MPCQP_ERR_INVALID_ARG, and nothing launched: what mpcqp_plant_step_device rejects; with d_terrain,
  * terrain_rows < 1, or terrain_rows < batch without d_episode_state.
- * Left out: height fields and steps, foot slip, trunk-ground contact.  The episode stage's height envelope
+ * Left out: foot slip, trunk-ground contact (uneven ground is mpcqp_plant_step_field_device's).  The episode stage's height envelope
  * (height_min / height_max) stays the world z of the trunk, so a long walk uphill leaves it by height_max:
  * a caller who walks robots on slopes widens the bounds.                                                    */
 int32_t mpcqp_plant_step_terrain_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
@@ -970,6 +971,58 @@ int32_t mpcqp_plant_step_terrain_device(const mpcqp_plant_params* pp, double dt,
                                         const double* d_episode_state, int32_t batch, double* d_plant_state,
                                         const double* d_plant_init, double* d_sensors, double* d_plan_in,
                                         double* d_states, double* d_tq_records, double* d_plant_out, void* stream);
+
+/* ---- bilinear height-field ground: steps, stairs, rough terrain.  A tile is a grid of heights H[ny][nx], x the
+ * fast index, node (i, j) at (x0 + i cell, y0 + j cell).  The tiles of a call lie in one array
+ * d_heights [heights_len]; the header rows d_field [field_rows][MPCQP_HF_SIZE] describe them.  Several header rows
+ * may name the same MPCQP_HF_OFFSET (many start poses on one tile), and tiles may differ in size.             */
+#define MPCQP_HF_X0 0            /* world x of node column 0                                                */
+#define MPCQP_HF_Y0 1            /* world y of node row 0                                                   */
+#define MPCQP_HF_CELL 2          /* node spacing, > 0                                                       */
+#define MPCQP_HF_MU 3            /* friction coefficient (mpcqp_plant_params.mu is not read)                */
+#define MPCQP_HF_NX 4            /* nodes along x, >= 2 (an integer held as a double, as NY and OFFSET)     */
+#define MPCQP_HF_NY 5            /* nodes along y, >= 2                                                     */
+#define MPCQP_HF_OFFSET 6        /* index of H[0][0] in d_heights                                           */
+#define MPCQP_HF_SIZE 8          /* 7 used, padded to a multiple of 4 doubles                               */
+
+/* mpcqp_plant_step_wrench_device on the ground of a height field.  d_field == NULL is
+ * mpcqp_plant_step_wrench_device, bit for bit.  The lookup at a world point p (contraction off):
+ *     u = (p_x - x0) / cell,  i = floor(u) clamped to [0, nx - 2],  fu_raw = u - i,  fu = min(max(fu_raw, 0), 1)
+ * and v, j, fv likewise along y; h00 = H[j][i], h10 = H[j][i+1], h01 = H[j+1][i], h11 = H[j+1][i+1];
+ *     a = h00 + fu (h10 - h00),  b = h01 + fu (h11 - h01),  h = a + fv (b - a)
+ *     gx = ((h10 - h00) + fv ((h11 - h01) - (h10 - h00))) / cell      (0 where fu_raw < 0 or fu_raw > 1)
+ *     gy = (b - a) / cell                                             (0 where fv_raw < 0 or fv_raw > 1)
+ *     s = sqrt((gx^2 + gy^2) + 1),  n = (-gx / s, -gy / s, 1 / s),  hgt(p) = (p_z - h) n_z.
+ * The ground continues flat beyond a tile's border.  The clamp of i and j is made on the double, before the
+ * conversion to an integer: no address outside the tile is formed for any p, finite or not.  hgt is the
+ * first-order normal distance; on a tile sampled from a plane it is the plane's own hgt, so the terrain entry
+ * cross-checks this one.  With each point's own hgt and n the four places of the terrain entry read:
+ *   1. fresh slot       a foot is held iff hgt(foot) <= 0, and a held foot is put at foot - hgt n.
+ *   2. ground reaction  fn = dot(n, f) with n at the held foot (a held foot keeps its position, so its normal is
+ *                       constant while it is held); the let-go rule and the cone scaling as on the plane, with
+ *                       the header row's mu.
+ *   3. touchdown        a swing foot lands iff hgt(foot) <= 0 && dot(n, v_foot) < 0, and is then put on the
+ *                       surface as in 1.
+ *   4. fallen           status 2.0 iff hgt(pos) < min_height, with h and n under the trunk.
+ * Unchanged: a held foot does not slip; MPCQP_PL_FOOT_FORCE is the world f_z; the row is chosen once per tick, as
+ * the terrain row is (robot b takes row (int) d_episode_state[b][MPCQP_ES_POOL], or row b without an episode
+ * slot); the episode stage's height envelope stays the world z, so a caller who climbs stairs widens it.
+ *   A bad row is treated like a non-finite torque row: 3.0 in MPCQP_PT_STATUS, nothing else written that tick,
+ * nothing read outside the two arrays, and the robot carries on at the next good row.  A row is bad when its
+ * index is outside [0, field_rows), when a header entry is non-finite, or when cell <= 0, nx < 2, ny < 2,
+ * OFFSET < 0 or OFFSET + nx ny > heights_len.  The heights themselves are not checked on the device: a
+ * non-finite height gives non-finite results for the robots that step on it.  The host packer
+ * (mpcqp.pack_height_field) rejects non-finite heights.
+ *   MPCQP_ERR_INVALID_ARG, and nothing launched: what mpcqp_plant_step_wrench_device rejects; with d_field,
+ * field_rows < 1, field_rows < batch without d_episode_state, d_heights == NULL, or heights_len < 4.
+ * Left out: overhangs, a riser's vertical face as anything but one steep cell (a step is a cell-wide ramp), foot
+ * slip, trunk-ground contact.                                                                               */
+int32_t mpcqp_plant_step_field_device(const mpcqp_plant_params* pp, double dt, const double* d_joint_torques,
+                                      const double* d_wrench, const double* d_field, int32_t field_rows,
+                                      const double* d_heights, int32_t heights_len, const double* d_episode_state,
+                                      int32_t batch, double* d_plant_state, const double* d_plant_init,
+                                      double* d_sensors, double* d_plan_in, double* d_states, double* d_tq_records,
+                                      double* d_plant_out, void* stream);
 
 /* The stage is stateless: every draw is a function of the Philox key `seed`, the robot index, and
  * MPCQP_ES_EPISODE / MPCQP_ES_TICK of the robot's episode slot, which it only reads.  So a restart needs no
@@ -1003,7 +1056,7 @@ int32_t mpcqp_plant_step_terrain_device(const mpcqp_plant_params* pp, double dt,
  * Left out: noise on the quaternion and on MPCQP_PL_FOOT_FORCE (the plant writes the foot force in place and two
  * stages read it), the payload's inertia, per-robot plant mass, foot slip.  (Per-robot friction and inclined
  * ground are rows of mpcqp_plant_step_terrain_device, chosen per episode through the pool index, not drawn
- * here; height fields and steps are left out there.)                                                        */
+ * here; uneven ground is the tiles of mpcqp_plant_step_field_device.)                                        */
 #define MPCQP_DS_JOINT_POS 0     /* indices of mpcqp_disturb_params.sigma                                  */
 #define MPCQP_DS_JOINT_VEL 1
 #define MPCQP_DS_IMU_ACC 2

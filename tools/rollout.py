@@ -38,6 +38,14 @@ friction restart with its start pose), three more:
              beside the ground's pitch along each robot's heading, and the root_euler_d[1] the plan stage wrote
   full_mu    the full_walk setup on level ground whose mu is MU_SET[row % 4]; its line carries the end reasons per mu
 
+and, with the plant's ground as a height-field table parallel to the pool (ControlTick(field=)), two more:
+
+  mpc_field  the mpc_ep setup standing level on a pool of start poses at random places and headings on three tiles:
+             rolling ground of 3 cm amplitude, a 5 cm step and stairs of 8 cm (one-cell risers of 5 cm), the height
+             envelope widened to the pool's trunk heights.  Its line carries the end reasons per tile
+  full_steps the full_walk setup heading for a step of STEP_SET[row % 5] m whose riser lies STEP_AHEAD m in front of
+             the front feet; its line carries, per step height, the end reasons and the distance walked
+
 These report episodes completed, the end-reason histogram, ticks/s and medians of the logged episodes' metrics
 from the device's totals and log, read once after the last replay; they never rerun with a read per tick.
 
@@ -147,7 +155,9 @@ def episode_pool(P, q_leg, tilt, seed, height=None):
 
 
 EPISODE_FORMS = ("mpc_ep", "full_ep", "full_walk", "servo_ep", "full_push", "full_noise", "mpc_slope", "full_slope",
-                 "full_mu")
+                 "full_mu", "mpc_field", "full_steps")
+FIELD_CELL, FIELD_NX, FIELD_NY, FIELD_X0, FIELD_Y0, FIELD_MU = 0.05, 49, 25, -0.8, -0.6, 0.6
+FIELD_TILES, STEP_SET, STEP_AHEAD = ("rolling", "step", "stairs"), (0.0, 0.02, 0.04, 0.06, 0.08), 0.1
 SLOPE_GRID, SLOPE_MAX, SLOPE_MU, SLOPE_HEIGHT, MU_SET = 5, 0.2, 0.6, 0.25, (0.2, 0.4, 0.6, 0.8)
 PUSH_START, PUSH_TICKS, PUSH_FORCE, PUSH_DIRS, PUSH_BIN = 100, 40, (0.0, 300.0), 16, 25.0
 NOISE_SIGMA, NOISE_BIAS = (0.005, 0.1, 0.2, 0.02), (0.1, 0.01)
@@ -163,6 +173,59 @@ def slope_pool(q_leg, seed):
     flat, _ = start_rows(pitch.size, q_leg, 0.0, seed)
     init, euler = mpcqp.place_on_terrain(flat, terrain)
     return mpcqp.pack_episode_pool(init, euler, init[:, :3]), terrain
+
+
+def field_grid():
+    x = (FIELD_X0 + FIELD_CELL * np.arange(FIELD_NX))[None, :] + np.zeros((FIELD_NY, 1))
+    y = (FIELD_Y0 + FIELD_CELL * np.arange(FIELD_NY))[:, None] + np.zeros((1, FIELD_NX))
+    return x, y, lambda at: np.clip((x - at) / FIELD_CELL, 0.0, 1.0)  # a riser: one cell wide
+
+
+def field_pool(q_leg, seed):
+    """(pool rows, (header rows, heights), a label per pool row) of mpc_field: the stance q_leg placed level by
+    place_on_field at a random place within +-0.3 m and a random heading on tile row % 3."""
+    x, y, riser = field_grid()
+    tiles = [0.03 * np.sin(2 * np.pi * x / 0.9 + 0.4) * np.cos(2 * np.pi * y / 1.3 - 0.2), 0.05 * riser(0.0),
+             0.08 * (riser(-0.35) + riser(-0.05) + riser(0.25) + riser(0.55))]
+    which = np.arange(POOL) % 3
+    rows, heights = mpcqp.pack_height_field(tiles, FIELD_X0, FIELD_Y0, FIELD_CELL, FIELD_MU, share=which)
+    flat, e = start_rows(POOL, q_leg, 0.0, seed)
+    flat[:, :2] = np.random.default_rng(seed + 1).uniform(-0.3, 0.3, (POOL, 2))
+    init, euler = mpcqp.place_on_field(flat, rows, heights, np.arange(POOL))
+    return mpcqp.pack_episode_pool(init, euler, init[:, :3]), (rows, heights), [FIELD_TILES[k] for k in which]
+
+
+def steep_starts(pool, field):
+    """Per pool row: whether a foot of the start stance stands on a facet steeper than the friction angle."""
+    from mpcqp.plant import _feet_body, _quat_rot
+    init = pool[:, :_lib.PI_SIZE]
+    P = init.shape[0]
+    feet = init[:, None, :3] + np.einsum("bij,blj->bli", _quat_rot(init[:, 3:7]),
+                                         _feet_body(mpcqp.default_plant_params(), init[:, 7:19].reshape(P, 4, 3)))
+    n = mpcqp.field_lookup(field[0], field[1], np.arange(P), feet)[1]
+    return (np.sqrt(1.0 / n[..., 2] ** 2 - 1.0) > FIELD_MU).any(1)
+
+
+def steps_pool(q_leg, seed):
+    """(pool rows, (header rows, heights), a label per pool row) of full_steps: the stance q_leg heading along +x
+    (within 0.05 rad) towards a step up of STEP_SET[row % 5] whose riser begins STEP_AHEAD in front of the front
+    feet, at a y within +-0.2 m."""
+    x, y, riser = field_grid()
+    which = np.arange(POOL) % len(STEP_SET)
+    rows, heights = mpcqp.pack_height_field([h * riser(0.0) for h in STEP_SET], FIELD_X0, FIELD_Y0, FIELD_CELL, FIELD_MU,
+                                            share=which)
+    flat, _ = start_rows(POOL, q_leg, 0.0, seed)
+    rng = np.random.default_rng(seed + 1)
+    yaw = rng.uniform(-0.05, 0.05, POOL)
+    zero = np.zeros(POOL)
+    flat[:, 3:7] = np.stack([np.cos(yaw / 2), zero, zero, np.sin(yaw / 2)], 1)
+    pp = mpcqp.default_plant_params()
+    front = er.fk(np.asarray(q_leg, dtype=np.float64).reshape(1, 1, 3), np.array(pp.rho_opt).reshape(1, 4, 3)[:, :1],
+                  np.array(pp.rho_fix).reshape(1, 4, 5)[:, :1])[0, 0, 0]
+    flat[:, 0] = -STEP_AHEAD - front
+    flat[:, 1] = rng.uniform(-0.2, 0.2, POOL)
+    init, euler = mpcqp.place_on_field(flat, rows, heights, np.arange(POOL))
+    return mpcqp.pack_episode_pool(init, euler, init[:, :3]), (rows, heights), [f"{h:.2f}" for h in np.array(STEP_SET)[which]]
 
 
 def make_episode(form, B, seed):
@@ -204,9 +267,16 @@ def make_episode(form, B, seed):
         grow = SLOPE_HEIGHT if form == "full_slope" else 0.0
         over = dict(height_min=stand * float(terrain[:, 2].min()) - 0.05 - grow, height_max=stand + 0.05 + grow)
         kw["terrain"] = terrain
+    labels = None
+    if form == "mpc_field":
+        kw, comp = {}, False
+        pool, kw["field"], labels = field_pool([0.0, 0.8, -1.6], seed)
+        over = dict(height_min=float(pool[:, 2].min()) - 0.05, height_max=float(pool[:, 2].max()) + 0.05)
+    if form == "full_steps":
+        pool, kw["field"], labels = steps_pool(full_stance()[0], seed)
     if form == "full_mu":
         kw["terrain"] = mpcqp.pack_terrain(np.tile([0.0, 0.0, 1.0], (POOL, 1)), 0.0, np.array(MU_SET)[np.arange(POOL) % 4])
-    if form in ("full_walk", "full_slope", "full_mu"):
+    if form in ("full_walk", "full_slope", "full_mu", "full_steps"):
         over = {} if form != "full_slope" else over
         scripts = mpcqp.pack_episode_scripts([[(0, (0, 0, 0), (0, 0, 0), False),
                                                (WALK_AT, (WALK_VX, 0, 0), (0, 0, 0), True)]])
@@ -223,6 +293,8 @@ def make_episode(form, B, seed):
     k = ControlTick(B, dt=DT, plant=pp, episode=ep, episode_pool=pool, episode_scripts=scripts, episode_log_len=8,
                     **kw)
     caller_rows(k, B, np.zeros((B, 3)), np.zeros(B), comp)  # the constants; the stage writes the desired values
+    k.field_labels = labels
+    k.field_steep = steep_starts(pool, kw["field"]) if form == "mpc_field" else None
     return k, extra
 
 
@@ -269,7 +341,9 @@ def run_episode(form, B, T, seed):
                     r.update({"noise_sigma": list(NOISE_SIGMA), "noise_bias": list(NOISE_BIAS)})
                 if form in ("mpc_slope", "full_slope", "full_mu"):
                     r.update(terrain_report(form, k, es, log))
-                if form in ("full_walk", "full_slope", "full_mu"):
+                if form in ("mpc_field", "full_steps"):
+                    r.update(field_report(form, k, log))
+                if form in ("full_walk", "full_slope", "full_mu", "full_steps"):
                     d = log["end"][:, :2] - log["start"][:, :2]
                     yaw = log["start"][:, 2]
                     fwd = d[:, 0] * np.cos(yaw) + d[:, 1] * np.sin(yaw)
@@ -323,6 +397,37 @@ def terrain_report(form, k, es, log):
                        if w.any() else None)
         rows.append(row)
     return {"terrain_rows": rows}
+
+
+def field_report(form, k, log):
+    """Per label of the pool rows (mpc_field: the tile; full_steps: the step height): the logged episodes, their end
+    reasons, and for full_steps the distance walked along the start heading and the height climbed by the episodes that
+    reached the toggle."""
+    from mpcqp import episode as me
+    labels = np.array(k.field_labels)
+    lrow = log["pool"].astype(int)
+    rows = []
+    for v in sorted(set(labels)):
+        m = labels[lrow] == v
+        row = {"ground": v, "episodes": int(m.sum()),
+               "length_median": float(np.median(log["length"][m])) if m.any() else None,
+               "end_reasons": {nm: int((log["reason"][m] == i).sum()) for i, nm in enumerate(me.END_NAMES)},
+               "lost_share": float(np.mean(log["reason"][m] != me.END_NAMES.index("timeout"))) if m.any() else None}
+        if form == "mpc_field":  # the starts with a foot on a facet steeper than the friction angle (a riser), apart
+            steep = k.field_steep[lrow]
+            lost = log["reason"] != me.END_NAMES.index("timeout")
+            row.update(pool_rows=int((labels == v).sum()), pool_rows_with_a_foot_on_a_riser=int(k.field_steep[labels == v].sum()),
+                       episodes_from_those=int((m & steep).sum()), lost_from_those=int((m & steep & lost).sum()),
+                       lost_from_the_others=int((m & ~steep & lost).sum()))
+        if form == "full_steps":
+            w = m & (log["length"] > WALK_AT)
+            d = log["end"][:, :2] - log["start"][:, :2]
+            fwd = d[:, 0] * np.cos(log["start"][:, 2]) + d[:, 1] * np.sin(log["start"][:, 2])
+            row.update(reached_the_toggle=int(w.sum()),
+                       forward_m_median=float(np.nanmedian(fwd[w])) if w.any() else None,
+                       forward_m_max=float(np.nanmax(fwd[w])) if w.any() else None)
+        rows.append(row)
+    return {"field_rows": rows, "field_mu": FIELD_MU, "step_ahead": STEP_AHEAD if form == "full_steps" else None}
 
 
 def push_curve(k, robot, log):

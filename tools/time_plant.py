@@ -10,6 +10,10 @@ graph-replayed control tick with and without it (HIP events, 3 warm-up runs, med
                                   motion, so the four differ by their code alone)
   plant_kernel_slope_substeps4_ms the terrain instantiation with the fleet standing slope-parallel on planes of
                                   pitch and roll in +-0.2 rad
+  plant_kernel_{terrain,field_level,field_rolling}_substeps{1,4}_ms   (--field) the field instantiation beside the
+                                  plane one: a level terrain row, a level 33 x 25 tile per robot (the same motion,
+                                  so the two differ by their code alone), and the fleet standing on one shared tile
+                                  of rolling ground (3 cm amplitude, 5 cm cells) at random places and headings
   tick_graph_mpc_plant            ControlTick(plant=), MPC-only and truth-fed, closing its own loop
   tick_graph_mpc                  the same tick object captured without its last stage (what the tick enqueued
                                   before the stage existed).  Each repetition snapshots every buffer of the tick,
@@ -20,9 +24,9 @@ graph-replayed control tick with and without it (HIP events, 3 warm-up runs, med
 
 The stage's share of the tick is the median of the 20 paired differences over the median tick without it;
 each form also prints the quartiles and extremes of its 20 repetitions.
-usage: python tools/time_plant.py [--batch 4096] [--kernels-only] [--flat-only]
+usage: python tools/time_plant.py [--batch 4096] [--kernels-only] [--flat-only] [--field]
 (--kernels-only: the plant kernel's lines alone; --flat-only: without the terrain instantiations, for an A/B against a
-library from before they existed, given by MPCQP_LIB)"""
+library from before they existed, given by MPCQP_LIB; --field: the lines of the field instantiation alone)"""
 import argparse
 import json
 import os
@@ -48,6 +52,7 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--flat-only", action="store_true")
+    ap.add_argument("--field", action="store_true")
     args = ap.parse_args()
     B = args.batch
     f64 = dict(dtype=torch.float64, device="cuda")
@@ -55,8 +60,9 @@ def main():
     out = {"batch": B, "warmup": WARMUP, "runs": RUNS}
 
     # ---- the kernel alone ----
-    def plant_alone(substeps, stance, wrench=False, terrain=None):
-        """terrain: None, "level" or "slope"; with either the launch goes through the terrain entry point."""
+    def plant_alone(substeps, stance, wrench=False, terrain=None, field=None):
+        """terrain: None, "level" or "slope"; with either the launch goes through the terrain entry point.
+        field: None, "level" or "rolling"; with either the launch goes through the field entry point."""
         pp = mpcqp.default_plant_params(substeps=substeps)
         slot = torch.zeros((B, mpcqp.plant_state_size()), **f64)
         rows = {n: torch.zeros((B, w), **f64) for n, w in (("sn", _lib.SN_SIZE), ("pl", _lib.PL_SIZE),
@@ -78,12 +84,30 @@ def main():
             flat, _ = start_rows(B, list(pp.default_joint_pos)[:3], 0.0, 2)
             init = torch.from_numpy(mpcqp.place_on_terrain(flat, t_rows)[0]).cuda()
             tr = torch.from_numpy(t_rows).cuda()
+        hf = None
+        if field is not None:
+            rng = np.random.default_rng(5)
+            x = (-0.8 + 0.05 * np.arange(33))[None, :] + np.zeros((25, 1))
+            y = (-0.6 + 0.05 * np.arange(25))[:, None] + np.zeros((1, 33))
+            tile = 0.03 * np.sin(2 * np.pi * x / 0.9 + 0.4) * np.cos(2 * np.pi * y / 1.3 - 0.2)
+            if field == "level":  # a tile of its own per robot, as every robot has a terrain row of its own
+                f_rows, heights = mpcqp.pack_height_field([0.0 * tile] * B, -0.8, -0.6, 0.05, pp.mu)
+            else:
+                f_rows, heights = mpcqp.pack_height_field([tile], -0.8, -0.6, 0.05, pp.mu, share=np.zeros(B, int))
+            flat, _ = start_rows(B, list(pp.default_joint_pos)[:3], 0.0, 2)
+            if field == "rolling":
+                flat[:, :2] = rng.uniform(-0.3, 0.3, (B, 2))
+            init = torch.from_numpy(mpcqp.place_on_field(flat, f_rows, heights, np.arange(B), pp)[0]).cuda()
+            hf = (torch.from_numpy(f_rows).cuda(), torch.from_numpy(heights).cuda())
         ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
         out_rows = (rows["sn"].data_ptr(), rows["pl"].data_ptr(), rows["st"].data_ptr(), rows["tq"].data_ptr(),
                     rows["po"].data_ptr(), stream)
 
         def step():
-            if tr is not None:
+            if hf is not None:
+                mpcqp.plant_step_field_device(pp, DT, tau.data_ptr(), ptr(wr), hf[0].data_ptr(), B, hf[1].data_ptr(),
+                                              hf[1].numel(), 0, B, slot.data_ptr(), ptr(init), *out_rows)
+            elif tr is not None:
                 mpcqp.plant_step_terrain_device(pp, DT, tau.data_ptr(), ptr(wr), tr.data_ptr(), B, 0, B,
                                                 slot.data_ptr(), ptr(init), *out_rows)
             elif wr is not None:
@@ -105,6 +129,15 @@ def main():
         assert np.all(po[:, _lib.PT_CONTACTS:_lib.PT_CONTACTS + 4] == (1.0 if stance else 0.0))
         return ms
 
+    if args.field:
+        for n in (1, 4):
+            out[f"plant_kernel_terrain_substeps{n}_ms"] = plant_alone(n, True, terrain="level")
+            out[f"plant_kernel_field_level_substeps{n}_ms"] = plant_alone(n, True, field="level")
+            out[f"plant_kernel_field_rolling_substeps{n}_ms"] = plant_alone(n, True, field="rolling")
+            out[f"plant_kernel_wrench_terrain_substeps{n}_ms"] = plant_alone(n, True, wrench=True, terrain="level")
+            out[f"plant_kernel_wrench_field_level_substeps{n}_ms"] = plant_alone(n, True, wrench=True, field="level")
+        print(json.dumps(out))
+        return
     out["plant_kernel_substeps1_ms"] = plant_alone(1, True)
     out["plant_kernel_substeps4_ms"] = plant_alone(4, True)
     out["plant_kernel_swing_substeps4_ms"] = plant_alone(4, False)
