@@ -16,7 +16,9 @@ def skew(v):
     return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
 
 
-def condensed_qp(rec, N, q_w, r_w):
+def condensed_parts(rec, N):
+    """(Aqp [13N][13], Bqp [13N][12N]): the part of condensed_qp that depends on the record only, not on the
+    weights."""
     dt = rec[REC_DT]
     yaw = rec[REC_EULER + 2]
     Ac = np.zeros((13, 13))
@@ -44,6 +46,12 @@ def condensed_qp(rec, N, q_w, r_w):
         Aqp[13 * i:13 * i + 13] = P
         for j in range(i + 1):
             Bqp[13 * i:13 * i + 13, 12 * j:12 * j + 12] = np.linalg.matrix_power(Ad, i - j) @ Bd[j]
+    return Aqp, Bqp
+
+
+def condensed_qp(rec, N, q_w, r_w, parts=None):
+    """H, g, C, lo, hi; parts: condensed_parts(rec, N) where the caller keeps it across weights."""
+    Aqp, Bqp = condensed_parts(rec, N) if parts is None else parts
     Q = np.diag(2 * np.tile(q_w, N))
     Rm = np.diag(2 * np.tile(r_w, N))
     H = Bqp.T @ Q @ Bqp + Rm

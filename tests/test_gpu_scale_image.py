@@ -137,9 +137,15 @@ def test_scale_image_matches_oracle_on_c4_sample(oracle):
 
 @pytest.mark.parametrize("N,qs,rs", [(10, 1e4, 1e4), (10, 1e6, 1.0), (20, 1e5, 1e3)])
 def test_scale_image_heavy_weights_exercise_exact_passes(oracle, N, qs, rs):
-    """Weights large enough that D H D's column norms matter: the passes the bound cannot decide
-    (scale_kernel regenerates H's columns there) and those it can, in one batch; both must give the
-    oracle's scale_data.  (With the Go1 weights every pass is decided by the bound.)"""
+    """Weights large enough that D H D's column norms matter; both kinds of robot must give the oracle's
+    scale_data.  What the three cases run (tests/scale_cases.py's census of the pass logic, asserted by
+    tests/test_scale_cases.py::test_census_of_the_heavy_weight_device_test): in all of them the SPD bound
+    wins a column's first-pass fmax, so the raw norms are the exact ones; then 50, 63 and 49 of the 64
+    robots run all ten passes decided by the bound, with a D that moves, and the other 14, 1 and 15 switch
+    to the exact passes (scale_kernel regenerates H's columns there) at pass 0, by the fmax test (ok2)
+    alone.  None reaches the fixed-point exit, fails the normalization test (ok1) or switches at a later
+    pass; the second and third case engage the 1e4 clamp.  (With the Go1 weights every pass is decided by
+    the bound and D = E = 1; tests/test_gpu_scale_paths.py covers the other paths.)"""
     st = mpcqp.synthetic_go1(64, seed=7, gait="trot")
     recs = mpcqp.assemble_compute_grf(st, N)
     p0 = mpcqp.default_params(N)
